@@ -67,13 +67,14 @@ def build(force: bool = False, verbose: bool = False) -> str:
     """Compile ``libpcmkm.so`` for gfx950 with hipcc (works without a GPU)."""
     if not force and not needs_build():
         return SO_PATH
-    # the translation units compile in parallel (-c) into an object cache outside
-    # the tree (a unit is rebuilt when it or a header it includes is newer than
-    # its object), then one link
+    # the translation units compile in parallel (-c) into this checkout's own
+    # object cache (the ignored build/ beside the sources: two checkouts never
+    # share objects; a unit is rebuilt when it or a header it includes is newer
+    # than its object), then one link
     import re
     from concurrent.futures import ThreadPoolExecutor
     inc = ["-I", os.path.join(REPO_DIR, "include")]
-    objdir = os.environ.get("PCM_OBJ_DIR") or os.path.join("/tmp", "pcm_build_objs")
+    objdir = os.environ.get("PCM_OBJ_DIR") or os.path.join(PKG_DIR, "build")
     os.makedirs(objdir, exist_ok=True)
 
     def deps(path, seen):

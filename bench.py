@@ -14,6 +14,21 @@ order before the timed region; that one-time layout is reported separately
 as ``layout_ms`` (it is not repeated per iteration).
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--n N] [--k K] [--d D]
+                       [--dump-outputs DIR] [--full]
+  A plain run does what the headline figure needs and nothing else: it builds
+  the cloud and its layout, warms up, times the K steps and prints the result
+  line (``value``, ``ms_per_step``, the layout and candidate-list figures).
+  ``--full`` adds every other leg, each a run of its own after the timed steps:
+  the per-kernel HIP-event pass behind ``roofline`` and
+  ``breakdown_ms_per_iter``, the whole fits, k-means++ seeding, the CPU
+  baselines (with ``--config 2`` the CPU/GPU parity check) and, when asked for,
+  ``--cloud`` and ``--stereo``.
+  ``--dump-outputs DIR`` writes what the timed path left its caller after the
+  last timed step (before any ``--full`` leg iterates further) as
+  ``DIR/<name>.npy``: ``centers`` (K x D float32), and the per-iteration
+  ``center_shift`` and ``stats_changed`` histories (float64, warm-up + timed
+  iterations).  The cloud and the initial centres are counter-based and seeded,
+  so the same arguments give the same inputs in every run and build.
   N > 1: either under torchrun (RANK/WORLD_SIZE set by the launcher), or plain
   ``python bench.py --gpus N``: the parent then starts N rank processes itself
   (before anything touches the GPU), one per GPU, and exits with their status.
@@ -230,6 +245,24 @@ def compute_roofline(n: int, k: int, d: int, cand_mean: float, launch_ms: float)
             "bruteforce_equivalent": brute, "bruteforce_equivalent_frac": brute / FP32_PEAK_TFLOPS}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict) -> dict:
+    """``--dump-outputs``: every array as ``path/<name>.npy`` (float32 stays, the
+    rest becomes float64), whole -- a run's centres and histories are far below
+    the 64 MB limit, which is checked.  Returns name -> shape for the result line."""
+    os.makedirs(path, exist_ok=True)
+    out = {n: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+           for n, a in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_MAX_BYTES}")
+    for n, a in out.items():
+        np.save(os.path.join(path, n + ".npy"), a)
+    return {n: list(a.shape) for n, a in out.items()}
+
+
 def _free_port() -> int:
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -430,7 +463,21 @@ def main():
                          "--gpus N); 5 = N=500M K=4096 D=4 f16 (needs >= 2 GPUs: 2^28 points per engine)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher test: each rank prints its RANK/WORLD_SIZE as JSON and exits before any GPU call")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg: the per-kernel event pass (roofline, "
+                         "breakdown), the whole fits, k-means++, the CPU baselines, and --cloud / --stereo / --fit "
+                         "when given; a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy: centers (K x D "
+                         "float32), center_shift and stats_changed (per iteration, float64)")
     args = ap.parse_args()
+    if not args.full:
+        extra = [f for f, on in (("--fit", args.fit), ("--stereo", args.stereo), ("--cloud", args.cloud)) if on]
+        if extra:
+            ap.error(f"{' '.join(extra)}: a leg beside the headline figure, run it with --full")
+        # the headline figure only: no event pass, no whole fits, no k-means++, no CPU baselines
+        args.no_cpu = args.no_kpp = args.no_events = True
+        args.fit_iters = 0
     if args.config == 2:
         args.n, args.k, args.d, args.dtype, args.steps = 1_000_000, 64, 3, "f32", 20
     elif args.config == 5:
@@ -591,6 +638,14 @@ def main():
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the timed path leaves its caller after the last timed step: the centres and the
+        # per-iteration histories, read here, before any later leg iterates this engine further
+        # (at N > 1 every rank holds the same centres: rank 0 writes them)
+        changed, shift = eng.history(total_iters)
+        dumped = dump_outputs(args.dump_outputs, {"centers": eng.centers().cpu().numpy(),
+                                                  "center_shift": shift, "stats_changed": changed})
     if not args.no_events and world == 1 and graph is None:
         tm = eng.timing_read()
     elif not args.no_events:
@@ -747,6 +802,12 @@ def main():
         }
         if getattr(args, "graph_error", None):
             out["graph_error"] = args.graph_error
+        out["full"] = bool(args.full)
+        if not args.full:
+            # no per-kernel event pass ran: its figures are --full's, not zeros here
+            del out["roofline"], out["breakdown_ms_per_iter"]
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if fit is not None:
             # whole-fit throughput (layout + iterations + final E-step + unpermute)
             out[f"fit_{fit['iters']}_iters_ms"] = fit["warm_ms"]

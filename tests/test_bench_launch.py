@@ -46,6 +46,34 @@ def test_failing_rank_fails_the_launch():
     assert rc != 0
 
 
+def test_legs_beside_the_headline_need_full():
+    """--fit / --stereo / --cloud are --full's legs: a plain run refuses them (before any GPU call)."""
+    for flag in ("--fit", "--stereo", "--cloud"):
+        rc, lines, err = _run("--gpus", "1", flag, "--dry-launch")
+        assert rc == 2 and not lines and "--full" in err, (flag, rc, err)
+    rc, lines, err = _run("--gpus", "1", "--full", "--fit", "--stereo", "--cloud", "--dry-launch")
+    assert rc == 0 and len(lines) == 1, err
+
+
+def test_dump_outputs_writes_npy(tmp_path):
+    """--dump-outputs' writer: one .npy per array, float32 kept, the rest float64, values unchanged."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    c = np.arange(12, dtype=np.float32).reshape(4, 3) / 7
+    ch = np.array([5, 0, 2 ** 40 + 1], dtype=np.int64)
+    out = tmp_path / "a" / "b"
+    shapes = bench.dump_outputs(str(out), {"centers": c, "stats_changed": ch})
+    assert shapes == {"centers": [4, 3], "stats_changed": [3]}
+    assert sorted(os.listdir(out)) == ["centers.npy", "stats_changed.npy"]
+    got = np.load(out / "centers.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, c)
+    got = np.load(out / "stats_changed.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, ch.astype(np.float64))
+
+
 def test_report_helpers_cpu():
     """The bench line's compute roofline and the NumPy-subsample and config-2 CPU legs (CPU only)."""
     import importlib.util

@@ -9,6 +9,6 @@ if [ $# -gt 0 ]; then
   tail -1 $T/pytest.txt
 fi
 for r in $(seq $REPS); do for v in $VALS; do
-  env $VAR=$v timeout -k 10 200 python bench.py --no-cpu --no-kpp --steps 20 > $T/b_${v}_$r.json 2> $T/b.err || { tail -20 $T/b.err; exit 1; }
+  env $VAR=$v timeout -k 10 200 python bench.py --full --no-cpu --no-kpp --steps 20 > $T/b_${v}_$r.json 2> $T/b.err || { tail -20 $T/b.err; exit 1; }
   tail -1 $T/b_${v}_$r.json | python -c "import json,sys; d=json.loads(sys.stdin.read()); f=d['fit']; print('$VAR=$v', 'step', round(d['ms_per_step'],4), 'layout', round(d['layout_ms'],3), 'fit warm', round(f['warm_ms'],3), 'cold', round(f['cold_ms'],3))"
 done; done

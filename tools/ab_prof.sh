@@ -6,7 +6,7 @@ T=gpurun_out/$1; VAR=$2; VALS=$3; shift 3; mkdir -p $T
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in $VALS; do
   t=${v//\//_}
-  env $VAR=$v timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $T/p_$t -o run -- python3 bench.py --no-cpu --no-kpp --steps 20 > $T/b_$t.json 2> $T/b_$t.err || { tail -20 $T/b_$t.err; exit 1; }
+  env $VAR=$v timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $T/p_$t -o run -- python3 bench.py --full --no-cpu --no-kpp --steps 20 > $T/b_$t.json 2> $T/b_$t.err || { tail -20 $T/b_$t.err; exit 1; }
   f=$(ls $T/p_$t/*/run_kernel_stats.csv $T/p_$t/run_kernel_stats.csv 2>/dev/null | head -1)
   python3 - "$f" "$VAR=$v" "$@" <<'PY'
 import csv, sys

@@ -4,9 +4,9 @@
 # usage: tools/clock_pmc.sh OUTDIR [bench args]
 OUT=$1; shift; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-timeout -k 10 -s KILL 240 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/clk -o run -- python3 bench.py --no-cpu --fit-iters 0 "$@" > $OUT/clk.txt 2>&1 || { tail -5 $OUT/clk.txt; exit 1; }
+timeout -k 10 -s KILL 240 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/clk -o run -- python3 bench.py --full --no-cpu --fit-iters 0 "$@" > $OUT/clk.txt 2>&1 || { tail -5 $OUT/clk.txt; exit 1; }
 for P in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 -s KILL 240 rocprofv3 --pmc $P --output-format csv -d $OUT/pmc_$P -o run -- python3 bench.py --no-cpu --no-graph --fit-iters 0 "$@" > $OUT/pmc_$P.log 2>&1 || { echo "FAIL pmc $P"; tail -5 $OUT/pmc_$P.log; exit 1; }
+  timeout -k 10 -s KILL 240 rocprofv3 --pmc $P --output-format csv -d $OUT/pmc_$P -o run -- python3 bench.py --full --no-cpu --no-graph --fit-iters 0 "$@" > $OUT/pmc_$P.log 2>&1 || { echo "FAIL pmc $P"; tail -5 $OUT/pmc_$P.log; exit 1; }
 done
 python3 tools/pmc_summary.py k_lloyd1 $OUT/pmc_FETCH_SIZE $OUT/pmc_WRITE_SIZE > $OUT/pmc_k_lloyd.json && cat $OUT/pmc_k_lloyd.json
 python3 - $OUT <<'PY'

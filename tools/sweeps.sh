@@ -20,7 +20,7 @@ line() {  # name, json file, python expression over d
 }
 run() {  # name, env assignments..., -- bench args...
   local name=$1; shift; local e=(); while [ "$1" != -- ]; do e+=("$1"); shift; done; shift
-  env "${e[@]}" timeout -k 10 200 python bench.py --no-cpu --fit-iters 0 "$@" > $T/$name.txt 2>&1 || { tail -5 $T/$name.txt; exit 1; }
+  env "${e[@]}" timeout -k 10 200 python bench.py --full --no-cpu --fit-iters 0 "$@" > $T/$name.txt 2>&1 || { tail -5 $T/$name.txt; exit 1; }
 }
 S12="--split --n 12500000"
 B="round(d['ms_per_step']*1e3,1), 'us/iter assign', round(d['breakdown_ms_per_iter']['assign']*1e3,1)"
@@ -64,7 +64,7 @@ case $P in
        tail -1 $T/pytest.txt
        bash tools/ab_c5.sh sw_lpt/c5 PCM_TILE_LPT "0 -1" 2 || exit 1
        for v in 0 -1 0 -1; do
-         PCM_TILE_LPT=$v timeout -k 10 200 python bench.py --split --no-cpu --fit-iters 0 --n 12500000 > $T/split_$v.json 2>&1 || { tail -5 $T/split_$v.json; exit 1; }
+         PCM_TILE_LPT=$v timeout -k 10 200 python bench.py --full --split --no-cpu --fit-iters 0 --n 12500000 > $T/split_$v.json 2>&1 || { tail -5 $T/split_$v.json; exit 1; }
          line "split12.5M LPT=$v" $T/split_$v.json "round(d['ms_per_step']*1e3,1), d['breakdown_ms_per_iter']['assign']"
        done
        bash tools/ab_env.sh sw_lpt/c3 PCM_TILE_LPT "0 -1" 2 ;;
