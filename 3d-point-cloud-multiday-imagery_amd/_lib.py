@@ -36,9 +36,9 @@ EXPORTS = [
     "pcm_layout_shard", "pcm_shard_hist", "pcm_shard_partition_workspace", "pcm_shard_partition",
     "pcm_shard_scatter_labels", "pcm_assign_kernel_name", "pcm_layout_stream_bytes", "pcm_engine_reserve",
     "pcm_xchg_create", "pcm_xchg_destroy", "pcm_xchg_handle", "pcm_xchg_open", "pcm_xchg_link", "pcm_xchg_allreduce",
-    "pcm_xchg_status", "pcm_iter_exchange",
+    "pcm_xchg_status", "pcm_iter_exchange", "pcm_sole_tiles",
 ]
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _lock = threading.Lock()
 _lib = None
@@ -136,6 +136,7 @@ def _declare(lib):
         "pcm_candidate_stats": ([P, ctypes.POINTER(D), ctypes.POINTER(I), ctypes.POINTER(I64), P], I),
         "pcm_tile_list_stats": ([P, ctypes.POINTER(I), ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I64), P],
                                 I),
+        "pcm_sole_tiles": ([P, ctypes.POINTER(I64), ctypes.POINTER(I64), P], I),
         "pcm_tile_list_detail": ([P, ctypes.POINTER(I64), ctypes.POINTER(I64), ctypes.POINTER(I64), P], I),
         "pcm_synth_uniform": ([P, I64, I, ctypes.c_uint64, I64, P], I),
         "pcm_assign_bruteforce": ([P, I64, I, P, I, P, P, P, P], I),

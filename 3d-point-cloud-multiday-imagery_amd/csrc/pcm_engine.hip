@@ -71,6 +71,12 @@ struct pcm_engine {
     bool use_xz = false;             // the current layout has a compressed stream
     bool tiles_lpt = false;          // tiles ordered longest candidate list first (PCM_TILE_LPT, A/B)
     size_t cap_xz = 0, cap_tmeta = 0;
+    // sole-owner tiles (SoleW, pcm_kernels.hpp): a tile whose cell has a one-entry list adds tsum, unread
+    long long *tsum = nullptr;       // [tile][d] fixed-point coordinate sums of the tile's points
+    uint32_t *tpos = nullptr;        // reordered tiles: layout tile index -> current position
+    uint32_t *torig = nullptr;       // ... and its inverse
+    size_t cap_tsum = 0, cap_tpos = 0, cap_torig = 0;
+    bool sole_on = true;             // PCM_SOLE=0 (A/B, read by pcm_fit_begin): every owner word stays 0
     // crowded layouts (tight clusters): Morton levels of the in-cell order and the tile lists
     int zlev = 0;
     float4 *tbox = nullptr;          // [tile][2] exact point box
@@ -271,13 +277,14 @@ void free_layout(pcm_engine *e) {
 void free_buffers(pcm_engine *e) {
     void *ps[] = {e->xs, e->perm, e->lab, e->cell_start, e->tiles, e->fc_cnt, e->fc_rec, e->fc_lab, e->tile_off, e->ws,
                   e->sub_start, e->xz, e->tmeta, e->tbox, e->tl_cnt, e->tl_rec, e->tl_lab, e->zcnt, e->dmap,
-                  e->cl_cnt, e->cl_idx};
+                  e->cl_cnt, e->cl_idx, e->tsum, e->tpos, e->torig};
     for (void *p : ps)
         if (p) (void)hipFree(p);
     e->dmap = nullptr; e->cap_dmap = 0; e->has_dmap = false;
     e->xs = nullptr; e->perm = nullptr; e->lab = nullptr; e->cell_start = nullptr; e->tiles = nullptr;
     e->tile_off = nullptr; e->ws = nullptr; e->sub_start = nullptr; e->cap_sub = 0;
     e->xz = nullptr; e->tmeta = nullptr; e->cap_xz = e->cap_tmeta = 0; e->use_xz = false;
+    e->tsum = nullptr; e->tpos = nullptr; e->torig = nullptr; e->cap_tsum = e->cap_tpos = e->cap_torig = 0;
     e->tbox = nullptr; e->tl_cnt = nullptr; e->tl_rec = nullptr; e->tl_lab = nullptr; e->zcnt = nullptr;
     e->cap_tbox = e->cap_tlc = e->cap_tlr = e->cap_tll = e->cap_zcnt = 0; e->zlev = 0;
     e->fc_cnt = nullptr; e->fc_rec = nullptr; e->fc_lab = nullptr;
@@ -660,13 +667,12 @@ int pcm_layout_build(pcm_engine *e, const void *X, const int32_t *q, int64_t gid
     choose_grid(e);
     const long long nc = e->g.ncells;
     const size_t ts = tsize(e->dtype);
-    // points per tile (<= TILE): PCM_TILE_CAP for tuning sweeps only
-    static const uint32_t tcap = [] {
+    // points per tile (<= TILE): PCM_TILE_CAP for tuning sweeps and tests only (read at every layout)
+    {
         const char *v = std::getenv("PCM_TILE_CAP");
         const int c = v ? std::atoi(v) : TILE;
-        return (uint32_t)std::min(TILE, std::max(4 * TPB, c));
-    }();
-    e->tile_cap = tcap;
+        e->tile_cap = (uint32_t)std::min(TILE, std::max(4 * TPB, c));
+    }
     // every cell holds ceil(count / cap) <= count / cap + 1 tiles
     e->ntiles_cap = nc + n / e->tile_cap + 1;
     e->ntiles = -1;
@@ -691,6 +697,7 @@ int pcm_layout_build(pcm_engine *e, const void *X, const int32_t *q, int64_t gid
         e->cap_fc = std::min(f0, f1);
     }
     HIPCHK(ensure(e->tiles, e->cap_tiles, (size_t)e->ntiles_cap * sizeof(uint4)));
+    HIPCHK(ensure(e->tsum, e->cap_tsum, (size_t)std::max(1LL, e->ntiles_cap) * e->d * sizeof(long long)));
     HIPCHK(hipMemsetAsync(e->fc_rec, 0, (size_t)nc * CAPF * sizeof(float4), s));
     HIPCHK(hipMemsetAsync(e->fc_lab, 0, (size_t)nc * CAPF * sizeof(int32_t), s));
     HIPCHK(hipMemsetAsync(e->fc_cnt, 0, (size_t)nc * sizeof(uint32_t), s));
@@ -782,8 +789,18 @@ int pcm_layout_build(pcm_engine *e, const void *X, const int32_t *q, int64_t gid
         HIPCHK(ensure(e->xz, e->cap_xz, (size_t)align_up(e->npad) * 8));   // whole 256-point blocks (zword)
         HIPCHK(ensure(e->tmeta, e->cap_tmeta, (size_t)e->ntiles_cap * sizeof(uint4)));
         k_tile_compress<<<(int)std::max(1LL, e->ntiles_cap), 256, 0, s>>>((const float *)e->xs, e->tiles, e->ntiles_dev, e->tmeta,
-                                                           e->xz, e->zpts);
+                                                           e->xz, e->zpts, e->qe, e->tsum);
         LAUNCHCHK();
+    } else {   // the tiles' fixed-point sums (k_tile_compress writes them on its way)
+        rc = dispatch_td(e->dtype, e->d, [&](auto T, auto DD) -> int {
+            using TT = decltype(T);
+            constexpr int D = decltype(DD)::value;
+            k_tile_sums<TT, D><<<(int)std::max(1LL, e->ntiles_cap), 256, 0, s>>>((const TT *)e->xs, e->tiles, e->ntiles_dev,
+                                                                                 e->qe, e->tsum);
+            LAUNCHCHK();
+            return 0;
+        });
+        if (rc) return rc;
     }
     if (e->zlev > 0) {   // crowded layout: exact tile boxes and tile-list storage
         HIPCHK(ensure(e->tbox, e->cap_tbox, (size_t)e->ntiles_cap * 2 * sizeof(float4)));
@@ -820,7 +837,8 @@ static int launch_candidates(pcm_engine *e, hipStream_t s, int gate);
 // and the XCD ranges (profiles/rd6_tile_lpt_ab.txt).  The statistics are exact
 // integers, so the order changes no result.  PCM_TILE_LPT = 0 / 1 forces it.
 static int tiles_order_lpt(pcm_engine *e, hipStream_t s) {
-    static const int mode = [] { const char *v = std::getenv("PCM_TILE_LPT"); return v ? std::atoi(v) : -1; }();
+    const char *lv = std::getenv("PCM_TILE_LPT");   // read at every fit start (A/B runs, tests)
+    const int mode = lv ? std::atoi(lv) : -1;
     const bool want = mode == 1 || (mode < 0 && (e->d >= 4 || e->ntiles <= 16LL * e->num_cu));
     if (!want || e->zlev > 0 || e->ntiles < 2) return 0;   // crowded layouts: tile boxes and lists are per tile
     const unsigned nt = (unsigned)e->ntiles;
@@ -830,19 +848,28 @@ static int tiles_order_lpt(pcm_engine *e, hipStream_t s) {
         return fail(PCM_E_HIP, "tile order: sort size");
     const size_t o_k1 = align_up((size_t)nt * 4), o_v0 = o_k1 + align_up((size_t)nt * 4), o_v1 = o_v0 + align_up((size_t)nt * 4),
                  o_t2 = o_v1 + align_up((size_t)nt * 4), o_m2 = o_t2 + align_up((size_t)nt * 16),
-                 o_tmp = o_m2 + align_up((size_t)nt * 16), need = o_tmp + sort_bytes;
+                 o_s2 = o_m2 + align_up((size_t)nt * 16), o_o2 = o_s2 + align_up((size_t)nt * e->d * 8),
+                 o_tmp = o_o2 + align_up((size_t)nt * 4), need = o_tmp + sort_bytes;
     if (ensure(e->ws, e->cap_ws, need) != hipSuccess) return fail(PCM_E_NOMEM, "tile order scratch");
+    HIPCHK(ensure(e->tpos, e->cap_tpos, (size_t)nt * sizeof(uint32_t)));
+    HIPCHK(ensure(e->torig, e->cap_torig, (size_t)nt * sizeof(uint32_t)));
     char *wb = (char *)e->ws;
     uint32_t *k0 = (uint32_t *)wb, *k1 = (uint32_t *)(wb + o_k1), *v0 = (uint32_t *)(wb + o_v0), *v1 = (uint32_t *)(wb + o_v1);
     uint4 *t2 = (uint4 *)(wb + o_t2), *m2 = (uint4 *)(wb + o_m2);
+    long long *s2 = (long long *)(wb + o_s2);
+    uint32_t *o2 = (uint32_t *)(wb + o_o2);
     k_tile_lpt_keys<<<blocks_for(nt), 256, 0, s>>>(e->tiles, e->fc_cnt, nt, k0, v0);
     LAUNCHCHK();
     size_t sb = sort_bytes;
     if (rocprim::radix_sort_pairs((void *)(wb + o_tmp), sb, k0, k1, v0, v1, (size_t)nt, 0u, 16u, s) != hipSuccess)
         return fail(PCM_E_HIP, "tile order: sort");
-    k_tile_gather<<<blocks_for(nt), 256, 0, s>>>(e->tiles, e->use_xz ? e->tmeta : nullptr, v1, nt, t2, m2);
+    // (a layout's first reorder starts from the layout order: torig = identity)
+    k_tile_gather<<<blocks_for(nt), 256, 0, s>>>(e->tiles, e->use_xz ? e->tmeta : nullptr, v1, nt, t2, m2, e->tsum, s2, e->d,
+                                                 e->tiles_lpt ? e->torig : nullptr, o2, e->tpos);
     LAUNCHCHK();
     HIPCHK(hipMemcpyAsync(e->tiles, t2, (size_t)nt * sizeof(uint4), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->tsum, s2, (size_t)nt * e->d * sizeof(long long), hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(e->torig, o2, (size_t)nt * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (e->use_xz) HIPCHK(hipMemcpyAsync(e->tmeta, m2, (size_t)nt * sizeof(uint4), hipMemcpyDeviceToDevice, s));
     e->tiles_lpt = true;
     return 0;
@@ -882,6 +909,10 @@ int pcm_fit_begin(pcm_engine *e, const float *C0, double tol, int max_iter, void
     e->ctrl_host.max_iter = (uint32_t)max_iter;
     e->ctrl_host.tol = tol;
     HIPCHK(hipMemcpyAsync(e->ctrl, &e->ctrl_host, sizeof(Ctrl), hipMemcpyHostToDevice, s));
+    {   // read per fit, so tests and A/B runs can switch it between fits of one process
+        const char *v = std::getenv("PCM_SOLE");
+        e->sole_on = !(v && std::atoi(v) == 0);
+    }
     e->fit_ready = true;
     // candidate lists of C0 (later iterations get theirs from k_lists / the resume path)
     if (int rc2 = launch_candidates(e, s, 0)) return rc2;
@@ -934,6 +965,16 @@ static int ensure_coarse(pcm_engine *e) {
 // config-5 shape 485 vs 536 us.
 static int lloyd_grid(const pcm_engine *e) { return (int)std::max(1LL, e->ntiles >= 0 ? e->ntiles : e->ntiles_cap); }
 
+// Owner words of the current layout for the list builders (SoleW).
+static SoleW sole_args(const pcm_engine *e) {
+    SoleW sw;
+    sw.tiles = e->tiles;
+    sw.tile_off = e->tile_off;
+    sw.tpos = e->tiles_lpt ? e->tpos : nullptr;
+    sw.on = e->sole_on ? 1 : 0;
+    return sw;
+}
+
 static int launch_candidates(pcm_engine *e, hipStream_t s, int gate) {
     return dispatch_d(e->d, [&](auto DD) -> int {
         constexpr int D = decltype(DD)::value;
@@ -946,12 +987,12 @@ static int launch_candidates(pcm_engine *e, hipStream_t s, int gate) {
             cl.in_cnt = e->cl_cnt;
             cl.in_idx = e->cl_idx;
             k_cand<D, 2><<<(int)n_mid(e), CAND_TPB, 0, s>>>(e->g, e->C, e->k, e->fc_cnt, e->fc_rec, e->fc_lab, e->ctrl,
-                                                             gate, 1, e->cref, cl);
+                                                             gate, 1, e->cref, cl, sole_args(e));
             LAUNCHCHK();
             return 0;
         }
         k_cand<D><<<(int)(e->g.ncoarse * bpc), CAND_TPB, 0, s>>>(e->g, e->C, e->k, e->fc_cnt, e->fc_rec, e->fc_lab,
-                                                                 e->ctrl, gate, bpc, e->cref, CoarseL{});
+                                                                 e->ctrl, gate, bpc, e->cref, CoarseL{}, sole_args(e));
         LAUNCHCHK();
         return 0;
     });
@@ -1010,6 +1051,7 @@ static LloydArgs lloyd_args(pcm_engine *e) {
     A.tmeta = e->use_xz ? e->tmeta : nullptr;
     A.npad = e->npad;
     A.tiles = e->tiles;
+    A.tsum = e->tsum;
     A.ntiles = e->ntiles_dev;
     A.fc_rec = e->fc_rec;
     A.fc_lab = e->fc_lab;
@@ -1176,12 +1218,12 @@ static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bo
                         k_updlists<D, RV, true><<<nlist + 1, CAND_TPB, lds, s>>>(
                             from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->cref,
                             e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha, e->drift_kappa * wmin, e->g,
-                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc);
+                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc, sole_args(e));
                     else
                         k_updlists<D, RV, false><<<nlist, CAND_TPB, lds, s>>>(
                             from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->cref,
                             e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha, e->drift_kappa * wmin, e->g,
-                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc);
+                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc, sole_args(e));
                 };
                 if (e->k <= CAND_TPB) fused(std::integral_constant<int, 1>{});
                 else fused(std::integral_constant<int, 2>{});
@@ -1215,19 +1257,19 @@ static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bo
                 const char *lt = std::getenv("PCM_LISTS4_TPB");
                 if (lt && std::atoi(lt) == 512)
                     k_lists<D, 2><<<(int)n_mid(e), CAND_TPB, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
-                                                                      e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl);
+                                                                      e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl, sole_args(e));
                 else
                     k_lists<D, 2, false, 256><<<(int)n_mid(e), 256, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
-                                                                             e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl);
+                                                                             e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl, sole_args(e));
             } else if (e->k <= LISTS_STAGE_MAX) {   // centres staged in LDS
                 const int bpc = cand_bpc(e);
                 k_lists<D, 4, true><<<(int)(e->g.ncoarse * bpc), CAND_TPB, (size_t)e->k * sizeof(float4), s>>>(
-                    e->g, e->Cn, e->C, e->cref, e->k, e->ctrl, e->fc_cnt, e->fc_rec, e->fc_lab, bpc, CoarseL{});
+                    e->g, e->Cn, e->C, e->cref, e->k, e->ctrl, e->fc_cnt, e->fc_rec, e->fc_lab, bpc, CoarseL{}, sole_args(e));
             } else {
                 const int bpc = cand_bpc(e);
                 k_lists<D><<<(int)(e->g.ncoarse * bpc), CAND_TPB, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
                                                                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc,
-                                                                           CoarseL{});
+                                                                           CoarseL{}, sole_args(e));
             }
             LAUNCHCHK();
             return 0;
@@ -1600,6 +1642,23 @@ int pcm_candidate_stats(pcm_engine *e, double *mean, int *mx, int64_t *full_cell
     *mean = nonfull > 0 ? (double)h[0] / (double)nonfull : 0.0;
     *mx = (int)h[1];
     *full_cells = (int64_t)h[2];
+    return 0;
+}
+
+int pcm_sole_tiles(pcm_engine *e, int64_t *tiles, int64_t *points, void *stream) {
+    if (!e || !tiles || !points) return fail(PCM_E_ARG, "bad argument");
+    if (!e->layout_ready) return fail(PCM_E_STATE, "layout not built");
+    *tiles = *points = 0;
+    if (e->n == 0 || e->ntiles_cap <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(e->cand_stats, 0, 2 * sizeof(unsigned long long), s));
+    k_sole_stats<<<blocks_for(e->ntiles_cap), 256, 0, s>>>(e->tiles, e->ntiles_dev, e->cand_stats);
+    LAUNCHCHK();
+    unsigned long long h[2];
+    HIPCHK(hipMemcpyAsync(h, e->cand_stats, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *tiles = (int64_t)h[0];
+    *points = (int64_t)h[1];
     return 0;
 }
 

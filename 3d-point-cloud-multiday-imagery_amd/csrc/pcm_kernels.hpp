@@ -409,14 +409,26 @@ __global__ __launch_bounds__(256) void k_tile_lpt_keys(const uint4 *__restrict__
     idx[t] = t;
 }
 
+// The per-tile sums `tsum` ([tile][d] int64, k_tile_compress / k_tile_sums) move
+// with their tiles, and the list builders' map from a tile's layout-time index
+// (tile_off[cell] + i) to its current position is kept: torig (position ->
+// layout index; null = identity, the first reorder of a layout) is permuted,
+// tpos (its inverse) rewritten.
 __global__ __launch_bounds__(256) void k_tile_gather(const uint4 *__restrict__ tiles, const uint4 *__restrict__ tmeta,
                                                      const uint32_t *__restrict__ idx, unsigned nt,
-                                                     uint4 *__restrict__ t2, uint4 *__restrict__ m2) {
+                                                     uint4 *__restrict__ t2, uint4 *__restrict__ m2,
+                                                     const long long *__restrict__ tsum, long long *__restrict__ s2, int d,
+                                                     const uint32_t *__restrict__ torig, uint32_t *__restrict__ o2,
+                                                     uint32_t *__restrict__ tpos) {
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     if (t >= nt) return;
     const uint32_t j = idx[t];
     t2[t] = tiles[j];
     if (tmeta) m2[t] = tmeta[j];
+    for (int a = 0; a < d; ++a) s2[(size_t)t * d + a] = tsum[(size_t)j * d + a];
+    const uint32_t o = torig ? torig[j] : j;
+    o2[t] = o;
+    tpos[o] = t;
 }
 
 // Compressed point stream (fp32, D = 3).  Inside one tile (one cell, <= TILE
@@ -455,7 +467,8 @@ __host__ __device__ __forceinline__ size_t zword(size_t i) { return (i >> 2) * 8
 
 __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__ xs, const uint4 *__restrict__ tiles,
                                                        const uint32_t *__restrict__ ntiles, uint4 *__restrict__ tmeta,
-                                                       unsigned *__restrict__ xz, unsigned long long *__restrict__ zpts) {
+                                                       unsigned *__restrict__ xz, unsigned long long *__restrict__ zpts,
+                                                       QExp qe, long long *__restrict__ tsum) {
     const unsigned t = blockIdx.x;
     if (t >= *ntiles) return;
     const uint4 tr = tiles[t];
@@ -487,6 +500,10 @@ __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__
         return __float_as_uint(k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w)));
     };
     unsigned mn[3] = {~0u, ~0u, ~0u}, mx[3] = {0u, 0u, 0u}, sor[3] = {0u, 0u, 0u}, sand[3] = {1u, 1u, 1u};
+    // the tile's fixed-point coordinate sums (tsum, sole-owner tiles of k_lloyd1),
+    // compressed or raw: a thread's <= 4 GPT points of |xq| < 2^25 fit int32
+    static_assert(4 * GPT <= 32, "per-thread fixed-point sums stay below 2^31");
+    int fs[3] = {0, 0, 0};
 #pragma unroll
     for (int u = 0; u < GPT; ++u) {
         const unsigned gg = g0 + (unsigned)tid + 256u * u;
@@ -501,13 +518,18 @@ __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__
                 mx[a] = max(mx[a], b);
                 sor[a] |= b >> 31;
                 sand[a] &= b >> 31;
+                fs[a] += fixed_i(__uint_as_float(b), qe.q[a]);
             }
         }
     }
     __shared__ unsigned smn[4][3], smx[4][3], sso[4][3], ssa[4][3];
+    __shared__ long long ssum[4][3];
     __shared__ uint4 meta;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
+        long long fl = fs[a];
+        for (int o = 32; o > 0; o >>= 1) fl += __shfl_xor(fl, o);
+        if (lane == 0) ssum[wv][a] = fl;
         for (int o = 32; o > 0; o >>= 1) {
             mn[a] = min(mn[a], (unsigned)__shfl_xor((int)mn[a], o));
             mx[a] = max(mx[a], (unsigned)__shfl_xor((int)mx[a], o));
@@ -520,6 +542,7 @@ __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__
     if (tid == 0) {
         unsigned w[3], lo[3], total = 0;
         bool ok = true;
+        for (int a = 0; a < 3; ++a) tsum[(size_t)t * 3 + a] = (ssum[0][a] + ssum[1][a]) + (ssum[2][a] + ssum[3][a]);
         for (int a = 0; a < 3; ++a) {
             unsigned m0 = ~0u, m1 = 0u, so = 0u, sa = 1u;
             for (int k = 0; k < 4; ++k) { m0 = min(m0, smn[k][a]); m1 = max(m1, smx[k][a]); so |= sso[k][a]; sa &= ssa[k][a]; }
@@ -570,6 +593,32 @@ __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__
             }
         }
     }
+}
+
+// tsum[t][a] = sum over the tile's points of fixed_i(x_a, q_a), for the layouts
+// k_tile_compress does not see (fp16, D != 3, PCM_XZ=0): one block per tile.
+template <typename T, int D>
+__global__ __launch_bounds__(256) void k_tile_sums(const T *__restrict__ xs, const uint4 *__restrict__ tiles,
+                                                   const uint32_t *__restrict__ ntiles, QExp qe,
+                                                   long long *__restrict__ tsum) {
+    const unsigned t = blockIdx.x;
+    if (t >= *ntiles) return;
+    const uint4 tr = tiles[t];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    long long fs[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) fs[a] = 0;
+    for (unsigned i = tr.y + tid; i < tr.z; i += 256)
+#pragma unroll
+        for (int a = 0; a < D; ++a) fs[a] += fixed_i(to_f<T>(xs[xs_index<D>(i, a)]), qe.q[a]);
+    __shared__ long long ssum[4][MAXD];
+#pragma unroll
+    for (int a = 0; a < D; ++a) {
+        for (int o = 32; o > 0; o >>= 1) fs[a] += __shfl_xor(fs[a], o);
+        if (lane == 0) ssum[wv][a] = fs[a];
+    }
+    __syncthreads();
+    if (tid < D) tsum[(size_t)t * D + tid] = (ssum[0][tid] + ssum[1][tid]) + (ssum[2][tid] + ssum[3][tid]);
 }
 
 // ------------------------------------------------------------------ crowded cells: tile lists
@@ -797,10 +846,39 @@ struct CoarseL {
 // FC = 2: a mid cell (2^D children, D = 4 layouts) whose list REFINES its
 // coarse parent's k_coarse list -- the same exact test against the mid box --
 // so the fine lists prune ~2^D-times shorter lists than the coarse ones.
+// Owner words (tiles[t].w): 0 = k_lloyd1 streams the tile; 1 + j = the tile's
+// cell has the one-entry list {j}, so every point of it goes to centroid j
+// whatever its coordinates and k_lloyd1 adds the tile's layout-time sums (tsum)
+// instead of reading its points.  0 is always correct.  The thread that stores
+// a cell's list length (pair path: thread `ch` of child ch, which loaded the
+// cell's tile range before the passes so that no latency is left at the block's
+// end) stores the word of each of the cell's tiles, on every
+// list build (a longer list clears it; a refresh leaves the lists and so the
+// words as they are).  tile_off: the layout's first tile of every cell; tpos:
+// layout tile index -> current position once the tiles were reordered
+// (k_tile_gather), else null.  Cells of more than SOLE_MAXT tiles keep the 0 of
+// k_tile_write: the store loop of that one lane stays short (a cell holds
+// SOLE_MAXT x TILE = 32768 points only when the grid is far too coarse for the
+// cloud, where lists are long anyway).
+constexpr uint32_t SOLE_MAXT = 8;
+struct SoleW {
+    uint4 *tiles = nullptr;             // null: the caller keeps no owner words
+    const uint32_t *tile_off = nullptr;
+    const uint32_t *tpos = nullptr;
+    int on = 0;                         // 0: every word written is 0 (PCM_SOLE=0)
+};
+__device__ __forceinline__ void sole_store(const SoleW &sw, long long cell, uint32_t cnt, int label) {
+    if (!sw.tiles) return;
+    const uint32_t t0 = sw.tile_off[cell], t1 = sw.tile_off[cell + 1];
+    if (t1 - t0 > SOLE_MAXT) return;
+    const uint32_t w = (sw.on && cnt == 1u) ? 1u + (uint32_t)label : 0u;
+    for (uint32_t t = t0; t < t1; ++t) sw.tiles[sw.tpos ? sw.tpos[t] : t].w = w;
+}
+
 template <int D, int FC = 4, int TPB = CAND_TPB>
 __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K, uint32_t *__restrict__ fc_cnt,
                                           float4 *__restrict__ fc_rec, int32_t *__restrict__ fc_lab, int BPC,
-                                          double dl = 0.0, CoarseL cl = CoarseL{}) {
+                                          double dl = 0.0, CoarseL cl = CoarseL{}, SoleW sw = SoleW{}) {
     static_assert(FC == 4 || FC == 2, "children per axis");
     constexpr int CAP = cand_capc<D>();
     constexpr int FS = FC == 4 ? 2 : 1;   // log2(FC)
@@ -988,6 +1066,10 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
         __shared__ long long s_cell[CAND_MAXCH];
         __shared__ float4 s_ref[CAND_MAXCH];   // the child's reference centre (pass A)
         __shared__ double s_mr[CAND_MAXCH];    // max distance from the child's box to it (drift budget > 0)
+        // owner words: thread ch < nch (<= CAND_MAXCH < TPB: one child per thread) loads its
+        // cell's tile range here and stores the words after pass (C), the latency hidden
+        static_assert(CAND_MAXCH <= TPB, "one child per thread");
+        uint32_t ot0 = 0u, ot1 = 0u;
         for (int ch = tid; ch < nch; ch += TPB) {
             int f[MAXD];
             bool inside = true;
@@ -1005,6 +1087,11 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
                 s_ctr[ch][a] = (float)(0.5 * (blo[a] + bhi[a]));
             }
             s_cell[ch] = inside ? encode(f, g.G, D) : -1ll;
+            if (inside && sw.tiles) {
+                const long long cell = encode(f, g.G, D);
+                ot0 = sw.tile_off[cell];
+                ot1 = sw.tile_off[cell + 1];
+            }
         }
         __syncthreads();
         DBG_T(10);
@@ -1102,6 +1189,17 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
             ch += dch;
             if (l >= (int)mp) { l -= (int)mp; ++ch; }
         }
+        if (sw.tiles && tid < nch && s_cell[tid] >= 0 && ot1 - ot0 <= SOLE_MAXT) {   // sole_store, ranges preloaded
+            const unsigned long long *wb = cbits + tid * nwc;
+            uint32_t total = 0;
+            int first = 0;   // the lowest kept position: the owner of a one-entry list
+            for (int w = nwc - 1; w >= 0; --w) {
+                total += __popcll(wb[w]);
+                if (wb[w]) first = w * 64 + __builtin_ctzll(wb[w]);
+            }
+            const uint32_t ow = (sw.on && total == 1u) ? 1u + (uint32_t)pidx[first] : 0u;
+            for (uint32_t t = ot0; t < ot1; ++t) sw.tiles[sw.tpos ? sw.tpos[t] : t].w = ow;
+        }
         DBG_T(2);
         return;
     }
@@ -1119,7 +1217,10 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
             if (!inside) continue;   // wave-uniform
             const long long cell = encode(f, g.G, D);
             if (!g.prune) {
-                if (lane == 0) fc_cnt[cell] = FULL;
+                if (lane == 0) {
+                    fc_cnt[cell] = FULL;
+                    sole_store(sw, cell, FULL, 0);
+                }
                 continue;
             }
             double blo[MAXD], bhi[MAXD];
@@ -1165,7 +1266,7 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
             }
             const float4 r = PF ? C[bl] : prec[bl];
             const double mr = dl > 0.0 ? sqrt(maxdist<D>(blo, bhi, r)) : 0.0;
-            uint32_t total = 0;
+            uint32_t total = 0, first = 0;   // first: the lowest kept position (the owner of a one-entry list)
             for (uint32_t base = 0; base < mp; base += 64) {
                 const uint32_t l = base + lane;
                 const bool in = l < mp;
@@ -1179,9 +1280,13 @@ __device__ __forceinline__ void cand_body(const Grid &g, const float4 *C, int K,
                     fc_rec[cell * CAPF + pos] = c;
                     fc_lab[cell * CAPF + pos] = j;
                 }
+                if (total == 0u && bal) first = base + (uint32_t)__builtin_ctzll(bal);
                 total += __popcll(bal);
             }
-            if (lane == 0) fc_cnt[cell] = total <= (uint32_t)CAPF ? total : FULL;
+            if (lane == 0) {
+                fc_cnt[cell] = total <= (uint32_t)CAPF ? total : FULL;
+                sole_store(sw, cell, total, PF ? (int)first : pidx[first]);
+            }
         }
     };
     if (pfull) child(std::integral_constant<bool, true>{});
@@ -1196,7 +1301,7 @@ template <int D, int FC = 4>
 __global__ __launch_bounds__(CAND_TPB) void k_cand(Grid g, const float4 *__restrict__ C, int K,
                                               uint32_t *__restrict__ fc_cnt, float4 *__restrict__ fc_rec,
                                               int32_t *__restrict__ fc_lab, Ctrl *__restrict__ ctrl, int gate,
-                                              int bpc, float4 *__restrict__ cref, CoarseL cl) {
+                                              int bpc, float4 *__restrict__ cref, CoarseL cl, SoleW sw) {
     if (gate && gated(ctrl)) return;
     float4 *ref = cref + (size_t)ctrl->ref_sel * K;
     for (long long j = blockIdx.x * (long long)CAND_TPB + threadIdx.x; j < K; j += (long long)gridDim.x * CAND_TPB)
@@ -1205,7 +1310,7 @@ __global__ __launch_bounds__(CAND_TPB) void k_cand(Grid g, const float4 *__restr
         ctrl->budget = 0.0;
         if (gate) ctrl->rebuilds += 1u;   // lists rebuilt at a relocation resume
     }
-    cand_body<D, FC>(g, C, K, fc_cnt, fc_rec, fc_lab, bpc, 0.0, cl);
+    cand_body<D, FC>(g, C, K, fc_cnt, fc_rec, fc_lab, bpc, 0.0, cl, sw);
 }
 
 // Coarse lists only (one block per coarse cell), for the child blocks of
@@ -1446,7 +1551,8 @@ struct LloydArgs {
     const unsigned *xz;             // compressed 8-B records (fp32 D = 3 tiles with tmeta .w bit 31), or null
     const uint4 *tmeta;             // per-tile compression record (k_tile_compress), or null
     long long npad;
-    const uint4 *tiles;             // {cell, start, end, -}
+    const uint4 *tiles;             // {cell, start, end, owner word (SoleW)}
+    const long long *tsum;          // [tile][D] fixed-point coordinate sums of the tile's points (layout time)
     const uint32_t *fc_cnt;         // candidate count per cell (FULL: all K)
     const uint32_t *ntiles;         // device: tile count of the layout
     const float4 *fc_rec;
@@ -1685,6 +1791,12 @@ __device__ __forceinline__ void scan4_s(const float4 *__restrict__ C, int mm, co
 // starts (the tile record -> count -> records chain cost ~3.8 us per block,
 // a quarter of its lifetime at config 3).  The list loads precede the point
 // loads, so the in-order vmcnt wait for the first work item covers them.
+// Sole-owner tiles (SoleW above): the tile record's owner word and the tile's
+// layout-time sums (tsum) arrive in that first latency too; when the word is
+// set the block adds the D sums and the point count to that centroid's row
+// and returns before any list or point load is issued -- the statistics are
+// exact integers, so the result is the one the streamed tile would give
+// (config 3: 23-24 % of the tiles, k_lloyd1 198 -> 169 us, profiles/sole_tiles_ab.txt).
 constexpr int LSPEC = 16;   // list records loaded before the count is known
 #ifndef PCM_MASK_MIN
 #define PCM_MASK_MIN 2
@@ -1758,16 +1870,37 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     uint4 tr = tiles[t];
     unsigned nt = *A.ntiles;
     unsigned gate = A.ctrl->halt | A.ctrl->done;
+    unsigned par = A.ctrl->iter & 1u;
+    // the tile's layout-time sums (uniform: scalar loads beside the record's): used
+    // only when the owner word is set, loaded here so that such a tile costs one
+    // latency in all
+    long long ts[D];
+#pragma unroll
+    for (int a = 0; a < D; ++a) ts[a] = A.tsum[(size_t)t * D + a];
     constexpr bool ZOK = sizeof(T) == 4 && D == 3;   // compressed tiles exist only for fp32 D = 3
     uint4 zm = make_uint4(0u, 0u, 0u, 0u);
     if (ZOK && A.tmeta) zm = A.tmeta[t];
-    asm volatile("" : "+s"(tr.x), "+s"(tr.y), "+s"(tr.z), "+s"(nt), "+s"(gate));   // keep the loads above the exits
+    asm volatile("" : "+s"(tr.x), "+s"(tr.y), "+s"(tr.z), "+s"(tr.w), "+s"(nt), "+s"(gate), "+s"(par));   // keep the loads above the exits
     asm volatile("" : "+s"(zm.x), "+s"(zm.y), "+s"(zm.z), "+s"(zm.w));
+#pragma unroll
+    for (int a = 0; a < D; ++a) asm volatile("" : "+s"(ts[a]));
     if (gate != 0u || t >= nt) return;
     DBG_L(0);
     DBG_LV(5, __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)));    // HW_REG_HW_ID, 32 bits
     DBG_LV(6, __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (15 << 11)));   // HW_REG_XCC_ID, 16 bits
     const unsigned cell = tr.x, start = tr.y, end = tr.z;
+    if (tr.w != 0u) {   // block-uniform: a sole-owner tile (SoleW), no list or point load is issued
+        DBG_LV(7, 1ull | ((unsigned long long)(end - start) << 16));
+        DBG_L(1);
+        DBG_L(2);
+        unsigned long long *pp = A.partials + (size_t)par * A.pstride + (size_t)(tr.w - 1u) * (D + 1);
+        unsigned long long v = (unsigned long long)(end - start);
+#pragma unroll
+        for (int a = 0; a < D; ++a) v = tid == a ? (unsigned long long)ts[a] : v;
+        if (tid <= D) atomicAdd(pp + tid, v);
+        DBG_L(3);
+        return;
+    }
     float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
     int l0 = 0;
     if (tid < LSPEC) {
@@ -1868,7 +2001,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
             for (int j = tid; j < mm * (D + 1); j += TPB) govf[j] = 0ull;
     }
     uint32_t *const myacc = acc + (tid & (AW - 1));
-    unsigned long long *prep = A.partials + (size_t)(A.ctrl->iter & 1u) * A.pstride;
+    unsigned long long *prep = A.partials + (size_t)par * A.pstride;
     __syncthreads();
     if constexpr (CROWD) {
         if (chunked) {   // block-uniform
@@ -2772,7 +2905,7 @@ template <int D, int FC = 4, bool STAGE = false, int TPB = CAND_TPB>
 __global__ __launch_bounds__(TPB) void k_lists(Grid g, const float4 *__restrict__ Cn, float4 *__restrict__ C,
                                                     float4 *__restrict__ cref, int K, const Ctrl *__restrict__ ctrl,
                                                     uint32_t *__restrict__ fc_cnt, float4 *__restrict__ fc_rec,
-                                                    int32_t *__restrict__ fc_lab, int bpc, CoarseL cl) {
+                                                    int32_t *__restrict__ fc_lab, int bpc, CoarseL cl, SoleW sw) {
     unsigned halt = ctrl->halt;
     unsigned mode = ctrl->lists;
     unsigned sel = ctrl->ref_sel;
@@ -2797,8 +2930,8 @@ __global__ __launch_bounds__(TPB) void k_lists(Grid g, const float4 *__restrict_
         refresh_body<D, TPB>(g, Cn, fc_cnt, fc_rec, fc_lab);
         return;
     }
-    if constexpr (STAGE) cand_body<D, FC, TPB>(g, cstage, K, fc_cnt, fc_rec, fc_lab, bpc, dl, cl);
-    else cand_body<D, FC, TPB>(g, Cn, K, fc_cnt, fc_rec, fc_lab, bpc, dl, cl);
+    if constexpr (STAGE) cand_body<D, FC, TPB>(g, cstage, K, fc_cnt, fc_rec, fc_lab, bpc, dl, cl, sw);
+    else cand_body<D, FC, TPB>(g, Cn, K, fc_cnt, fc_rec, fc_lab, bpc, dl, cl, sw);
 }
 
 // Centre update and candidate lists in ONE launch (D <= 3, K <= CAND_TPB * 2 =
@@ -2825,7 +2958,7 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
     unsigned long long *__restrict__ held, unsigned long long *__restrict__ prev, float4 *__restrict__ C,
     float4 *__restrict__ cref, unsigned long long *__restrict__ hist_changed, double *__restrict__ hist_shift,
     Ctrl *__restrict__ ctrl, double alpha, double dl_cap, Grid g, uint32_t *__restrict__ fc_cnt,
-    float4 *__restrict__ fc_rec, int32_t *__restrict__ fc_lab, int bpc) {
+    float4 *__restrict__ fc_rec, int32_t *__restrict__ fc_lab, int bpc, SoleW sw) {
     static_assert(R * CAND_TPB <= SHIFT_LANES && SHIFT_LANES % CAND_TPB == 0, "one tree lane per row");
     extern __shared__ __attribute__((aligned(16))) float4 cstage[];   // the K new centres
     DBG_T(13);
@@ -2955,7 +3088,7 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
         if (n_empty == 0ull && !pub_blk) {
             DBG_T(14);
             // this block's cells: rebuilt at the new centres with the new budget, or refreshed
-            if (rebuild) cand_body<D, 4>(g, cstage, K, fc_cnt, fc_rec, fc_lab, bpc, dl_new, CoarseL{});
+            if (rebuild) cand_body<D, 4>(g, cstage, K, fc_cnt, fc_rec, fc_lab, bpc, dl_new, CoarseL{}, sw);
             else refresh_body<D>(g, cstage, fc_cnt, fc_rec, fc_lab, nlist);
         }
     }
@@ -3283,6 +3416,20 @@ __global__ __launch_bounds__(256) void k_cand_stats(const uint32_t *__restrict__
     if (m == FULL) { atomicAdd(out + 2, 1ull); return; }
     atomicAdd(out, (unsigned long long)m);
     atomicMax(out + 1, (unsigned long long)m);
+}
+
+// Sole-owner tiles (owner word set) and their points, for diagnostics.
+__global__ __launch_bounds__(256) void k_sole_stats(const uint4 *__restrict__ tiles, const uint32_t *__restrict__ ntiles,
+                                                    unsigned long long *__restrict__ out /* tiles, points */) {
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const uint4 tr = t < (long long)*ntiles ? tiles[t] : make_uint4(0u, 0u, 0u, 0u);
+    const bool sole = tr.w != 0u;
+    unsigned long long nt = __popcll(__ballot(sole)), np = sole ? tr.z - tr.y : 0u;
+    for (int o = 32; o > 0; o >>= 1) np += __shfl_xor(np, o);
+    if ((threadIdx.x & 63) == 0 && nt) {
+        atomicAdd(out, nt);
+        atomicAdd(out + 1, np);
+    }
 }
 
 // ------------------------------------------------------------------ brute force

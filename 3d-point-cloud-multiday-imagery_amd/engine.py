@@ -237,6 +237,9 @@ class Engine:
         _lib.check(self.lib.pcm_candidate_stats(self.h, ctypes.byref(mean), ctypes.byref(mx), ctypes.byref(full),
                                                 _stream()), "pcm_candidate_stats")
         out = dict(mean=mean.value, max=mx.value, full_cells=full.value)
+        st, sp = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self.lib.pcm_sole_tiles(self.h, ctypes.byref(st), ctypes.byref(sp), _stream()), "pcm_sole_tiles")
+        out.update(sole_tiles=st.value, sole_points=sp.value)   # one-entry lists: tiles the assign kernel does not read
         z, ft, lt, ll = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         _lib.check(self.lib.pcm_tile_list_stats(self.h, ctypes.byref(z), ctypes.byref(ft), ctypes.byref(lt),
                                                 ctypes.byref(ll), _stream()), "pcm_tile_list_stats")

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PCM_ABI_VERSION 6
+#define PCM_ABI_VERSION 7
 
 enum pcm_dtype { PCM_F32 = 0, PCM_F16 = 1, PCM_F64 = 2 /* dense path only */ };
 
@@ -184,6 +184,11 @@ int pcm_layout_stream_bytes(pcm_engine *e, double *bytes, int64_t *compressed_po
 int pcm_assign_kernel_name(pcm_engine *e, char *buf, size_t n);
 /* Mean/max fine candidate-list length of the last iteration (synchronising). */
 int pcm_candidate_stats(pcm_engine *e, double *mean, int *max, int64_t *full_cells, void *stream);
+/* Sole-owner tiles of the current candidate lists: tiles whose cell has a
+ * one-entry list, which the assign kernel credits to that centroid from the
+ * tile's layout-time sums without reading its points, and the points they hold
+ * (synchronising; 0 / 0 with PCM_SOLE=0). */
+int pcm_sole_tiles(pcm_engine *e, int64_t *tiles, int64_t *points, void *stream);
 /* Crowded layouts (cells holding many tiles' worth of points, e.g. tight
  * clusters): the Morton levels of the in-cell point order (0: not crowded),
  * the tiles of cells whose list is FULL or longer than 16 at the last
