@@ -12,7 +12,11 @@ assemble_cloud(disparity, validity, max_disp=288)      -> per-pair (z,y,x) cloud
 KMeans(n_clusters, init, n_init, ...).fit_predict(X)   -> the reference's KMeans call site (core.py:227-228)
 dense_fit / dense_kmeanspp                             -> generic-D (float32/float64) Lloyd + k-means++ (GPU)
 photoconsistency_map / left_right_consistency          -> stereo consistency gathers (GPU, processing.py / disparity.py)
+lloyd_predict(X, centers, return_distance=, return_inertia=) -> LloydPrediction: labels of new points, no refit
+KMeans.predict / transform / fit_transform / score     -> sklearn's API for applying a fitted model
+dense_predict / dense_transform                        -> generic-D E-step and (n, K) distances for given centres
 kmeans_fuse(clouds, n_clusters, ...)                   -> napari layer tuples
+kmeans_assign(clouds, model)                           -> a later day's cloud labelled against a fused model
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -21,7 +25,8 @@ from .lloyd import LloydResult, lloyd_fit  # noqa: F401
 
 __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fuse", "HeightMapExtractor",
            "build_library", "kmeans_plusplus", "assemble_cloud", "KMeans", "dense_fit", "dense_kmeanspp",
-           "photoconsistency_map", "left_right_consistency"]
+           "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
+           "dense_transform", "DensePrediction", "kmeans_assign"]
 
 
 def __getattr__(name):
@@ -29,16 +34,19 @@ def __getattr__(name):
     if name == "Engine":
         from .engine import Engine
         return Engine
-    if name in ("kmeans_fuse", "HeightMapExtractor", "PREFIX"):
+    if name in ("kmeans_fuse", "kmeans_assign", "HeightMapExtractor", "PREFIX"):
         from . import plugin
         return getattr(plugin, name)
+    if name in ("lloyd_predict", "LloydPrediction"):
+        from . import predict
+        return getattr(predict, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans
     if name == "assemble_cloud":
         from .cloud import assemble_cloud
         return assemble_cloud
-    if name in ("dense_fit", "dense_kmeanspp"):
+    if name in ("dense_fit", "dense_kmeanspp", "dense_predict", "dense_transform", "DensePrediction"):
         from . import dense
         return getattr(dense, name)
     if name in ("photoconsistency_map", "left_right_consistency"):

@@ -37,8 +37,10 @@ EXPORTS = [
     "pcm_shard_scatter_labels", "pcm_assign_kernel_name", "pcm_layout_stream_bytes", "pcm_engine_reserve",
     "pcm_xchg_create", "pcm_xchg_destroy", "pcm_xchg_handle", "pcm_xchg_open", "pcm_xchg_link", "pcm_xchg_allreduce",
     "pcm_xchg_status", "pcm_iter_exchange", "pcm_sole_tiles",
+    "pcm_predict_workspace", "pcm_predict", "pcm_dense_predict", "pcm_dense_transform",
 ]
-ABI_VERSION = 7
+ABI_VERSION = 8
+DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
 
 _lock = threading.Lock()
 _lib = None
@@ -54,6 +56,11 @@ class PcmStatus(ctypes.Structure):
                 ("last_shift", ctypes.c_double), ("inertia_limbs", ctypes.c_uint64 * 3),
                 ("inertia_scale", ctypes.c_int32), ("inertia_overflow", ctypes.c_uint32),
                 ("list_rebuilds", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class PcmInertia(ctypes.Structure):
+    """pcm_inertia: the exact inertia limbs a predict call returns."""
+    _fields_ = [("limbs", ctypes.c_uint64 * 3), ("overflow", ctypes.c_uint32), ("scale", ctypes.c_int32)]
 
 
 def needs_build() -> bool:
@@ -173,6 +180,10 @@ def _declare(lib):
         "pcm_xchg_allreduce": ([P, P, I, P], I),
         "pcm_xchg_status": ([P, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint64), P], I),
         "pcm_iter_exchange": ([P, P, I, P], I),
+        "pcm_predict_workspace": ([I64, I, I, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_predict": ([P, I, I64, I, P, I, P, P, P, ctypes.POINTER(PcmInertia), P, P, ctypes.c_size_t, P], I),
+        "pcm_dense_predict": ([P, I, I64, I, P, I, P, P, P, ctypes.POINTER(PcmInertia), P, ctypes.c_size_t, P], I),
+        "pcm_dense_transform": ([P, I, I64, I, P, I, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -129,6 +129,32 @@ __global__ __launch_bounds__(256) void k_dense_assign(const T *__restrict__ X, l
     }
 }
 
+// KMeans.transform: out[i * k + j] = sqrt(dense_dist(x_i, c_j)).  A block takes
+// chunks of `rows` whole rows and walks their rows * k outputs flat, so the
+// lanes run along j and the row-major stores coalesce whatever k is; the lanes
+// of one row read the same x (broadcast).  Centres in LDS when they fit.
+template <typename T>
+__global__ __launch_bounds__(256) void k_dense_transform(const T *__restrict__ X, long long n, int d,
+                                                         const T *__restrict__ C, int k, T *__restrict__ out,
+                                                         int rows, int lds_c) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    T *scl = (T *)sm;
+    const T *sc = lds_c ? scl : C;
+    if (lds_c) {
+        for (int j = threadIdx.x; j < k * d; j += blockDim.x) scl[j] = C[j];
+        __syncthreads();
+    }
+    for (long long r0 = (long long)blockIdx.x * rows; r0 < n; r0 += (long long)gridDim.x * rows) {
+        const long long nr = n - r0 < rows ? n - r0 : rows;
+        const long long cnt = nr * k;
+        for (long long e = threadIdx.x; e < cnt; e += blockDim.x) {
+            const long long i = r0 + e / k;
+            const int j = (int)(e % k);
+            out[r0 * k + e] = sqrt(dense_dist<T>(X + i * d, sc + (size_t)j * d, d));
+        }
+    }
+}
+
 // Centre update, relocation, shift, convergence (one block of 256 threads).
 template <typename T>
 __global__ __launch_bounds__(256) void k_dense_update(const T *__restrict__ X, long long n, int d, T *__restrict__ C,
@@ -709,6 +735,89 @@ int pcm_dense_kmeanspp(const void *X, int64_t n, int d, int dtype, int k, int n_
             if (more) k_dkpp_locate<T><<<L, 1024, 0, s>>>((const T *)X, n, d, (const T *)closest, S, scale);
             if (hipGetLastError() != hipSuccess) return pcm_fail(PCM_E_HIP, "dense kmeanspp launch");
         }
+        return 0;
+    });
+}
+
+static int dense_pred_args(const void *X, int dtype, int64_t n, int d, const void *C, int k) {
+    if (d < 1 || d > PCM_DENSE_DMAX) return pcm_fail(PCM_E_ARG, "d must be 1..PCM_DENSE_DMAX");
+    if (k < 1) return pcm_fail(PCM_E_ARG, "k must be >= 1");
+    if (n < 0 || n >= (1LL << 31)) return pcm_fail(PCM_E_ARG, "n must be in [0, 2^31)");
+    if (dtype != PCM_F32 && dtype != PCM_F64) return pcm_fail(PCM_E_ARG, "dtype must be PCM_F32 or PCM_F64");
+    if ((!X && n > 0) || !C) return pcm_fail(PCM_E_ARG, "X or C is null");
+    return 0;
+}
+
+static int dense_num_cu() {
+    int dev = 0, ncu = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu < 1)
+        ncu = 256;
+    return ncu;
+}
+
+int pcm_dense_predict(const void *X, int dtype, int64_t n, int d, const void *C, int k, const double *maxabs,
+                      int32_t *labels, void *dist, pcm_inertia *inertia, void *workspace, size_t workspace_bytes,
+                      void *stream) {
+    if (int rc = dense_pred_args(X, dtype, n, d, C, k)) return rc;
+    if (!labels && n > 0) return pcm_fail(PCM_E_ARG, "labels is null");
+    if (inertia) {
+        if (!maxabs) return pcm_fail(PCM_E_ARG, "inertia limbs need maxabs");
+        std::memset(inertia, 0, sizeof(*inertia));
+        double bound = 0.0;
+        for (int a = 0; a < d; ++a) {
+            if (!std::isfinite(maxabs[a])) return pcm_fail(PCM_E_NONFINITE, "input contains NaN or Inf");
+            int ea = 0;
+            if (maxabs[a] > 0.0) (void)std::frexp(maxabs[a], &ea);
+            bound += std::ldexp(1.0, 2 * (ea + 1));   // (2 * 2^e_a)^2, as pcm_dense_begin
+        }
+        int eb = 0;
+        (void)std::frexp(bound * (1.0 + std::ldexp(1.0, -20)), &eb);
+        inertia->scale = 64 - eb;
+    }
+    if (n == 0) return 0;
+    static_assert(sizeof(DenseCtrl) <= PCM_DENSE_PREDICT_WS, "the control block fits the workspace");
+    if (!workspace || workspace_bytes < PCM_DENSE_PREDICT_WS) return pcm_fail(PCM_E_ARG, "workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    // k_dense_assign compares labels[i] (whatever the caller's buffer holds) with the new label and
+    // adds the count to ctrl->changed: the private block takes that unused count, and holds the limbs
+    DenseCtrl *ctrl = (DenseCtrl *)workspace;
+    if (hipMemsetAsync(ctrl, 0, sizeof(DenseCtrl), s)) return pcm_fail(PCM_E_HIP, "dense predict memset");
+    const size_t ts = tsz(dtype);
+    const int lds_c = (size_t)k * d * ts <= 64 * 1024 ? 1 : 0;
+    const size_t lds = lds_c ? (((size_t)k * d * ts + 15) / 16) * 16 : 0;
+    const int grid = (int)std::max(1LL, std::min<long long>((n + 255) / 256, (long long)dense_num_cu() * 4));
+    int rc = dispatch_t(dtype, [&](auto TT) -> int {
+        using T = decltype(TT);
+        k_dense_assign<T><<<grid, 256, lds, s>>>((const T *)X, n, d, (const T *)C, k, nullptr, labels, (T *)dist, nullptr,
+                                                 0, ctrl, 0, inertia ? ctrl->inert : nullptr,
+                                                 inertia ? inertia->scale : 0, lds_c);
+        if (hipGetLastError() != hipSuccess) return pcm_fail(PCM_E_HIP, "dense predict launch");
+        return 0;
+    });
+    if (rc || !inertia) return rc;
+    unsigned long long h[4];
+    if (hipMemcpyAsync(h, ctrl->inert, sizeof(h), hipMemcpyDeviceToHost, s) || hipStreamSynchronize(s))
+        return pcm_fail(PCM_E_HIP, "dense predict limbs");
+    for (int t = 0; t < 3; ++t) inertia->limbs[t] = h[t];
+    inertia->overflow = (uint32_t)std::min<unsigned long long>(h[3], 0xFFFFFFFFull);
+    return 0;
+}
+
+int pcm_dense_transform(const void *X, int dtype, int64_t n, int d, const void *C, int k, void *out, void *stream) {
+    if (int rc = dense_pred_args(X, dtype, n, d, C, k)) return rc;
+    if (!out && n > 0) return pcm_fail(PCM_E_ARG, "out is null");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t ts = tsz(dtype);
+    const int lds_c = (size_t)k * d * ts <= 64 * 1024 ? 1 : 0;
+    const size_t lds = lds_c ? (((size_t)k * d * ts + 15) / 16) * 16 : 0;
+    const int rows = (int)std::max(1LL, 4096LL / k);   // ~4096 outputs (16 per thread) per chunk
+    const int grid = (int)std::max(1LL, std::min<long long>((n + rows - 1) / rows, (long long)dense_num_cu() * 4));
+    return dispatch_t(dtype, [&](auto TT) -> int {
+        using T = decltype(TT);
+        k_dense_transform<T><<<grid, 256, lds, s>>>((const T *)X, n, d, (const T *)C, k, (T *)out, rows, lds_c);
+        if (hipGetLastError() != hipSuccess) return pcm_fail(PCM_E_HIP, "dense transform launch");
         return 0;
     });
 }

@@ -3464,4 +3464,77 @@ __global__ __launch_bounds__(256) void k_bruteforce(const float *__restrict__ X,
     }
 }
 
+// ------------------------------------------------------------------ predict
+// Centres (K, D) float32 -> the float4 records the list builders and the scans read.
+__global__ __launch_bounds__(256) void k_predict_pack(const float *__restrict__ Cg, int K, int D,
+                                                      float4 *__restrict__ C4) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= K) return;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < D; ++a) v[a] = Cg[(size_t)j * D + a];
+    C4[j] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+// Sort-free E-step for given centres (pcm_predict): the cloud is streamed once
+// in the caller's row order, one point per lane per round.  A lane bins its
+// point with the layout's arithmetic (sort_key_f: fp64 floor, clamped) and scans
+// its cell's exact candidate list (k_cand at drift budget 0: ids ascending, so
+// strict '<' keeps the lowest index on ties); a cell without a usable list
+// (FULL, i.e. more than CAPF candidates) and every point when g.prune == 0 scan
+// all K centres through uniform loads.  Nothing is accumulated per centroid, so
+// no order of the points is needed; raster-ordered clouds keep the lanes of a
+// wave in one or two cells, whose first few records stay cache resident.
+// dist (nullable): the canonical squared distance to the winner; inert_rep
+// (nullable): exact inertia limbs into the replica lines (k_inert_fold).
+template <typename T, int D>
+__global__ __launch_bounds__(TPB) void k_predict(const T *__restrict__ X, long long n, Grid g,
+                                                 const float4 *__restrict__ C, int K,
+                                                 const uint32_t *__restrict__ fc_cnt,
+                                                 const float4 *__restrict__ fc_rec,
+                                                 const int32_t *__restrict__ fc_lab, int32_t *__restrict__ labels,
+                                                 float *__restrict__ dist, unsigned long long *inert_rep, int iscale) {
+    unsigned long long ilo = 0ull, ihi = 0ull;
+    unsigned iovf = 0u;
+    const long long st = (long long)gridDim.x * TPB;
+    for (long long i = blockIdx.x * (long long)TPB + threadIdx.x; i < n; i += st) {
+        float x[D];
+#pragma unroll
+        for (int a = 0; a < D; ++a) x[a] = to_f<T>(X[i * D + a]);
+        uint32_t m = FULL;
+        long long cell = 0;
+        if (g.prune) {
+            int idx[MAXD];
+#pragma unroll
+            for (int a = 0; a < D; ++a) {
+                const int v = (int)floor(((double)x[a] - g.lo[a]) * g.inv[a]);
+                idx[a] = v < 0 ? 0 : (v >= g.G[a] ? g.G[a] - 1 : v);
+            }
+            cell = encode(idx, g.G, D);
+            m = fc_cnt[cell];
+        }
+        float bd;
+        int bj = 0;
+        if (m - 1u < (uint32_t)CAPF) {   // a list of 1..CAPF candidates
+            const float4 *rec = fc_rec + (size_t)cell * CAPF;
+            int bp = 0;
+            bd = dist_canon<D>(x, rec[0]);
+            for (uint32_t p = 1; p < m; ++p) {
+                const float dd = dist_canon<D>(x, rec[p]);
+                if (dd < bd) { bd = dd; bp = (int)p; }
+            }
+            bj = fc_lab[(size_t)cell * CAPF + bp];
+        } else {
+            bd = dist_canon<D>(x, C[0]);
+            for (int j = 1; j < K; ++j) {
+                const float dd = dist_canon<D>(x, C[j]);
+                if (dd < bd) { bd = dd; bj = j; }
+            }
+        }
+        labels[i] = bj;
+        if (dist) dist[i] = bd;
+        if (inert_rep) inert_add(ilo, ihi, iovf, bd, iscale);
+    }
+    if (inert_rep) inert_flush(ilo, ihi, iovf, inert_rep);
+}
+
 }  // namespace pcm

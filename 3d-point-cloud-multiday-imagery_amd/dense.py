@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 import torch
@@ -137,3 +138,63 @@ def dense_kmeanspp(X: torch.Tensor, n_clusters: int, *, random_state=None, n_loc
                                       umant.ctypes.data_as(ctypes.c_void_p), s, _ptr(idx), _ptr(ws), nbytes.value,
                                       _stream()), "pcm_dense_kmeanspp")
     return X[idx].clone(), idx
+
+
+@dataclass
+class DensePrediction:
+    labels: torch.Tensor                    # int32
+    distance: Optional[torch.Tensor]        # canonical SQUARED distance to the assigned centre, X's dtype
+    inertia: Optional[float]
+
+
+def _centres_for(X: torch.Tensor, centers) -> torch.Tensor:
+    C = torch.as_tensor(centers).to(device=X.device, dtype=X.dtype).contiguous()
+    if C.dim() != 2 or C.shape[1] != X.shape[1] or C.shape[0] < 1:
+        raise ValueError(f"centers must be (k, {X.shape[1]}) with k >= 1")
+    if not torch.isfinite(C).all():
+        raise ValueError("centers contain NaN or Inf")
+    if not torch.isfinite(X).all():
+        raise ValueError("input points contain NaN or Inf")
+    return C
+
+
+def dense_predict(X: torch.Tensor, centers: torch.Tensor, *, return_distance: bool = False,
+                  return_inertia: bool = False) -> DensePrediction:
+    """E-step of the dense path for given centres (sklearn ``_labels_inertia``,
+    _kmeans.py:1083-1108) in X's precision: labels, optionally the squared
+    distances and the exact inertia (scale from max |.| over ``X`` and ``centers``)."""
+    X = _check(X)
+    C = _centres_for(X, centers)
+    n, d = X.shape
+    k = C.shape[0]
+    lib = _lib.load()
+    labels = torch.empty(n, dtype=torch.int32, device=X.device)
+    dist = torch.empty(n, dtype=X.dtype, device=X.device) if return_distance else None
+    limbs = _lib.PcmInertia() if return_inertia else None
+    m = C.abs().amax(0).double()
+    if n:
+        m = torch.maximum(m, X.abs().amax(0).double())
+    maxabs = np.ascontiguousarray(m.cpu().numpy())
+    ws = torch.empty(_lib.DENSE_PREDICT_WS, dtype=torch.uint8, device=X.device)
+    _lib.check(lib.pcm_dense_predict(_ptr(X) if n else None, _dtype_code(X), n, d, _ptr(C), k,
+                                     maxabs.ctypes.data_as(ctypes.c_void_p), _ptr(labels) if n else None,
+                                     _ptr(dist) if (dist is not None and n) else None,
+                                     ctypes.byref(limbs) if limbs is not None else None, _ptr(ws),
+                                     _lib.DENSE_PREDICT_WS, _stream()), "pcm_dense_predict")
+    inertia = None
+    if limbs is not None:
+        inertia = inertia_from_limbs(list(limbs.limbs), limbs.scale, limbs.overflow)
+    return DensePrediction(labels=labels, distance=dist, inertia=inertia)
+
+
+def dense_transform(X: torch.Tensor, centers: torch.Tensor) -> torch.Tensor:
+    """``KMeans.transform`` (_kmeans.py:1135-1161): the (n, k) Euclidean distances
+    of every row to every centre, in X's dtype (sqrt of the canonical squared distance)."""
+    X = _check(X)
+    C = _centres_for(X, centers)
+    n, d = X.shape
+    k = C.shape[0]
+    out = torch.empty((n, k), dtype=X.dtype, device=X.device)
+    _lib.check(_lib.load().pcm_dense_transform(_ptr(X) if n else None, _dtype_code(X), n, d, _ptr(C), k,
+                                               _ptr(out) if n else None, _stream()), "pcm_dense_transform")
+    return out

@@ -15,6 +15,12 @@ This class keeps that API and restates the control flow of scikit-learn 1.7.2's
   clustering differs (``_is_same_clustering``, ``_k_means_common.pyx:314-328``);
   ``n_init='auto'`` is 1 for k-means++ / an array, 10 for ``'random'``.
 
+A fitted estimator is applied with ``predict`` / ``score`` (``_labels_inertia``,
+``:1067-1108``, ``:1163-1191``) and ``transform`` / ``fit_transform``
+(``:1110-1161``): X as given -- not centred -- against ``cluster_centers_``,
+through ``lloyd_predict`` / ``dense_predict`` (the engine ``_dense`` picks) and
+``dense_transform``.
+
 Every pass over the data runs in the HIP kernels (k-means++ seeding, Lloyd
 iterations, final E-step); the host holds only O(K) state plus the mean/var of
 the boundary, which mirror sklearn's own NumPy calls.  Dtypes follow sklearn
@@ -57,7 +63,8 @@ class KMeans:
 
     def __init__(self, n_clusters: int = 8, *, init="k-means++", n_init="auto", max_iter: int = 300,
                  tol: float = 1e-4, random_state=None, algorithm: str = "lloyd", float64_points: str = "dense",
-                 _fit: Optional[Callable] = None, _seed: Optional[Callable] = None):
+                 _fit: Optional[Callable] = None, _seed: Optional[Callable] = None,
+                 _predict: Optional[Callable] = None, _transform: Optional[Callable] = None):
         if float64_points not in ("dense", "float32"):
             raise ValueError("float64_points must be 'dense' or 'float32'")
         self.n_clusters = n_clusters
@@ -70,6 +77,10 @@ class KMeans:
         self.float64_points = float64_points
         self._fit = _fit      # tests: a CPU stand-in for (Xc, C0, max_iter, tol) -> (labels, centers, inertia, n_iter)
         self._seed = _seed    # tests: a CPU stand-in for k-means++ (Xc, k, RandomState) -> centers
+        # tests: CPU stand-ins for the E-step on given centres, (X, C) -> (labels, sqdist[, inertia])
+        # (without an inertia: the float64 sum of sqdist), and for transform, (X, C) -> (n, K) distances
+        self._predict = _predict
+        self._transform = _transform
 
     # ------------------------------------------------------------ GPU legs
     DENSE_LDS_BYTES = 64 * 1024        # the dense engine stages all K centres in LDS (pcm_dense.hip)
@@ -180,3 +191,80 @@ class KMeans:
 
     def fit_predict(self, X, y=None, sample_weight=None):
         return self.fit(X, sample_weight=sample_weight).labels_
+
+    # ------------------------------------------------------------ applying a fitted model
+    # sklearn 1.7.2: predict (_kmeans.py:1067-1108), transform / fit_transform (:1110-1161),
+    # score (:1163-1191).  X is used as given -- NOT centred -- against cluster_centers_.
+    def _check_test(self, X) -> np.ndarray:
+        """sklearn ``check_is_fitted`` + ``_check_test_data``: fitted, 2-D, finite,
+        float32 kept (everything else float64), ``n_features_in_`` features."""
+        if not hasattr(self, "cluster_centers_"):
+            raise NotFittedError("This KMeans instance is not fitted yet. Call 'fit' with appropriate arguments "
+                                 "before using this estimator.")
+        if hasattr(X, "detach"):
+            X = X.detach().cpu().numpy()
+        X = np.asarray(X)
+        X = np.ascontiguousarray(X, dtype=np.float32 if X.dtype == np.float32 else np.float64)
+        if X.ndim != 2:
+            raise ValueError("Expected a 2D array")
+        if X.shape[1] != self.n_features_in_:
+            raise ValueError(f"X has {X.shape[1]} features, but KMeans is expecting {self.n_features_in_} features "
+                             "as input.")
+        if not np.isfinite(X).all():
+            raise ValueError("Input X contains NaN or infinity.")
+        return X
+
+    def _gpu_predict(self, X: np.ndarray, C: np.ndarray):
+        """(labels, squared distances, inertia) of X against C on the engine ``_dense`` picks."""
+        import torch
+
+        if KMeans._dense(X, C.shape[0], self.float64_points):
+            from .dense import dense_predict
+            res = dense_predict(torch.from_numpy(X).cuda(), torch.from_numpy(C).cuda(), return_distance=True,
+                                return_inertia=True)
+        else:
+            from .predict import lloyd_predict
+            if X.dtype == np.float64:
+                warnings.warn("pcm_amd.KMeans: float64 points cast to float32 for the pruned engine (float64_points="
+                              "'float32'); labels may differ from a float64 prediction", RuntimeWarning, stacklevel=3)
+            res = lloyd_predict(torch.from_numpy(np.ascontiguousarray(X, np.float32)).cuda(),
+                                torch.from_numpy(np.ascontiguousarray(C, np.float32)).cuda(), return_distance=True,
+                                return_inertia=True)
+        torch.cuda.synchronize()
+        return res.labels.cpu().numpy(), res.distance.cpu().numpy(), float(res.inertia)
+
+    def _gpu_transform(self, X: np.ndarray, C: np.ndarray) -> np.ndarray:
+        import torch
+
+        from .dense import dense_transform
+        out = dense_transform(torch.from_numpy(X).cuda(), torch.from_numpy(C).cuda())
+        torch.cuda.synchronize()
+        return out.cpu().numpy()
+
+    def _labels_inertia(self, X):
+        X = self._check_test(X)
+        C = np.ascontiguousarray(self.cluster_centers_, dtype=X.dtype)   # the centres in X's precision
+        res = (self._predict or self._gpu_predict)(X, C)
+        labels, sq = res[0], res[1]
+        inertia = float(res[2]) if len(res) > 2 else float(np.sum(np.asarray(sq, dtype=np.float64)))
+        return np.asarray(labels, dtype=np.int32), inertia
+
+    def predict(self, X):
+        return self._labels_inertia(X)[0]
+
+    def score(self, X, y=None, sample_weight=None):
+        if sample_weight is not None and not np.all(np.asarray(sample_weight) == 1):
+            raise NotImplementedError("unit sample weights only (the reference's call site passes none)")
+        return -self._labels_inertia(X)[1]
+
+    def transform(self, X):
+        X = self._check_test(X)
+        C = np.ascontiguousarray(self.cluster_centers_, dtype=X.dtype)
+        return np.asarray((self._transform or self._gpu_transform)(X, C), dtype=X.dtype)
+
+    def fit_transform(self, X, y=None, sample_weight=None):
+        return self.fit(X, sample_weight=sample_weight).transform(X)
+
+
+class NotFittedError(ValueError, AttributeError):
+    """As ``sklearn.exceptions.NotFittedError``: raised by predict / transform / score before ``fit``."""

@@ -158,6 +158,59 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     return layers, result
 
 
+def _gpu_assign(X, C: np.ndarray):
+    """X: host (N, 3) float32 array, or the cloud already on the device -> (labels, squared distances, inertia)."""
+    import torch
+
+    from .predict import lloyd_predict
+
+    with _gpu_lock:
+        Xt = X.to(torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+        res = lloyd_predict(Xt, torch.from_numpy(np.ascontiguousarray(C, dtype=np.float32)).cuda(),
+                            return_distance=True, return_inertia=True)
+        torch.cuda.synchronize()
+        return res.labels.cpu().numpy(), res.distance.cpu().numpy(), float(res.inertia)
+
+
+def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None):
+    """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
+
+    ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
+    an ``export_fused`` file; its ``centers`` are used as they are.  Returns
+    (layers, result): one points layer with the per-point ``cluster`` (int32),
+    ``residual`` (Euclidean distance to the assigned centre, float64: a per-point
+    change measure against the model) and ``height``; ``result`` has labels,
+    distance (= residual), inertia, n_points.  Same boundary cast (float64 ->
+    float32) and ``device_clouds`` shortcut as ``kmeans_fuse``; ``assign`` lets
+    tests substitute (X, C) -> (labels, squared distances, inertia).
+    """
+    if not isinstance(model, dict):
+        model = load_fused(model)
+    C = np.ascontiguousarray(np.asarray(model["centers"], dtype=np.float64).astype(np.float32))
+    if C.ndim != 2 or C.shape[1] != 3 or C.shape[0] < 1:
+        raise ValueError("model centers must be (K, 3)")
+    clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
+    if not clouds:
+        raise ValueError("no point cloud layers to assign")
+    X = np.concatenate(clouds).astype(np.float32)          # boundary cast (SURVEY.md a4)
+    Xq = X
+    if device_clouds is not None and assign is None:
+        import torch
+        Xq = torch.cat([c.reshape(-1, 3) for c in device_clouds if c.numel()]).to(torch.float32)   # same rounding
+    labels, sq, inertia = (assign or _gpu_assign)(Xq, C)
+    labels = np.asarray(labels).astype(np.int32)
+    residual = np.sqrt(np.asarray(sq, dtype=np.float64))
+    layers = [
+        (X.astype(np.float64),
+         {"name": f"{PREFIX} Assigned {CLOUD_LAYER_SUFFIX}", "size": 2,
+          "properties": {"cluster": labels, "residual": residual, "height": _norm(X[:, 0].astype(np.float64))},
+          "scale": (1, 1, 1), "opacity": 0.8, "face_colormap": "turbo", "face_color": "cluster"},
+         "points"),
+    ]
+    return layers, dict(labels=labels, distance=residual, inertia=float(inertia), n_points=X.shape[0])
+
+
 class HeightMapExtractor(SatellitePlugin):
     """Multi-day 3D point clouds from WV3 stereo pairs, fused by GPU K-means."""
 
@@ -165,8 +218,13 @@ class HeightMapExtractor(SatellitePlugin):
 
     def __init__(self, base=None, n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                  fit: Optional[Callable] = None, init: str = "rows", seed: int = 1, stages=None,
-                 export_path=None, _assemble: Optional[Callable] = None):
+                 export_path=None, _assemble: Optional[Callable] = None, model=None,
+                 assign: Optional[Callable] = None):
         self._base = base
+        # model: a fitted model (kmeans_fuse result, load_fused dict or export_fused path); when given,
+        # run fuses nothing and labels the run's clouds against it (kmeans_assign)
+        self.model = model
+        self._assign = assign
         self._stages = stages
         self.export_path = export_path
         self._assemble = _assemble   # tests: a CPU stand-in for the GPU assembly (disparity, validity) -> (pts, h_norm)
@@ -201,6 +259,11 @@ class HeightMapExtractor(SatellitePlugin):
             dev_clouds.append(dev)
         if not host_clouds:
             return layers
+        if self.model is not None:
+            use_dev = self._assign is None and all(d is not None for d in dev_clouds)
+            assigned, self.last_result = kmeans_assign(host_clouds, self.model, assign=self._assign,
+                                                       device_clouds=dev_clouds if use_dev else None)
+            return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                               fit=self._fit, init=self.init,
@@ -240,6 +303,9 @@ class HeightMapExtractor(SatellitePlugin):
                       if kind == "points" and str(params.get("name", "")).endswith(CLOUD_LAYER_SUFFIX)]
             if not clouds:   # the pipeline returned only images (or an error layer): pass it through
                 return layers
+            if self.model is not None:
+                assigned, self.last_result = kmeans_assign(clouds, self.model, assign=self._assign)
+                return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path)
             return layers + fused

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define PCM_ABI_VERSION 7
+#define PCM_ABI_VERSION 8
 
 enum pcm_dtype { PCM_F32 = 0, PCM_F16 = 1, PCM_F64 = 2 /* dense path only */ };
 
@@ -229,6 +229,35 @@ int pcm_synth_uniform(float *out, int64_t n, int d, uint64_t seed, int64_t start
 int pcm_assign_bruteforce(const float *X, int64_t n, int d, const float *C, int k,
                           const int32_t *q, int32_t *labels, uint64_t *stats, void *stream);
 
+/* ---------------------------------------------------------------- predict
+ * Labels (and distances, inertia) of a cloud against GIVEN centres: the E-step
+ * of sklearn's KMeans.predict / score (_labels_inertia, sklearn/cluster/
+ * _kmeans.py:1083-1108) in the canonical arithmetic of pcm_final, without the
+ * layout sort -- the rows keep the caller's order.  X: device n*d rows
+ * (PCM_F32 or PCM_F16, d = 1..4); C: device float32[k*d], anywhere relative to
+ * X (finite; checked on the host).  labels: device int32[n]; dist (nullable):
+ * device float32[n], the canonical squared distance to the assigned centre.
+ * inertia (nullable, host): the exact limbs of sum trunc(dist * 2^scale) and
+ * the overflow count, scale derived from `q` (host int32[d], the fixed-point
+ * exponents of X AND C together, identical on every rank; used only for the
+ * inertia -- labels and distances never depend on it).  Multi-rank callers sum
+ * limbs and overflow over the ranks, then pcm_inertia_value.  info (nullable,
+ * host int64[3]): cells of the pruning grid, cells whose list is FULL (their
+ * points scan all k centres), summed length of the other lists; all 0 when no
+ * lists were built (k = 1, or coordinates near the fp32 range).
+ * Synchronises `stream` (centres, bounding box, and the host outputs);
+ * PCM_E_NONFINITE for NaN/Inf in X, PCM_E_ARG for NaN/Inf in C (k <= 2^24);
+ * n = 0 succeeds without any device call (the centres are then not checked).  workspace: caller-owned device memory of
+ * pcm_predict_workspace bytes. */
+typedef struct pcm_inertia {
+    uint64_t limbs[3];
+    uint32_t overflow;
+    int32_t scale;
+} pcm_inertia;
+int pcm_predict_workspace(int64_t n, int d, int k, size_t *bytes);
+int pcm_predict(const void *X, int dtype, int64_t n, int d, const float *C, int k, const int32_t *q, int32_t *labels,
+                float *dist, pcm_inertia *inertia, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
@@ -358,6 +387,24 @@ int pcm_dense_kmeanspp_workspace(int64_t n, int d, int dtype, int k, int n_local
 int pcm_dense_kmeanspp(const void *X, int64_t n, int d, int dtype, int k, int n_local_trials, int64_t first_index,
                        const uint64_t *umant, int scale, int64_t *indices, void *workspace, size_t workspace_bytes,
                        void *stream);
+
+/* Stateless E-step of the dense path for given centres (no pcm_dense object, no
+ * fit state): labels device int32[n]; dist (nullable) device n of dtype, the
+ * canonical squared distance to the assigned centre; inertia (nullable, host):
+ * exact limbs, scale from maxabs (host double[d]) = max |.| per feature over
+ * the rows of X AND C (needed only with inertia).  workspace: device memory of
+ * at least PCM_DENSE_PREDICT_WS bytes.  Synchronises when inertia is given.
+ * The kernel is the fit's E-step: it reads labels[i] before it writes it, to
+ * count changed labels (the count goes to the workspace and is not used), so
+ * labels must be readable memory; its content on entry does not matter. */
+#define PCM_DENSE_PREDICT_WS 256
+int pcm_dense_predict(const void *X, int dtype, int64_t n, int d, const void *C, int k, const double *maxabs,
+                      int32_t *labels, void *dist, pcm_inertia *inertia, void *workspace, size_t workspace_bytes,
+                      void *stream);
+/* sklearn KMeans.transform (_kmeans.py:1135-1161): out (device n*k of dtype,
+ * row-major) = sqrt of the canonical squared distance of row i to centre j,
+ * correctly rounded in dtype.  Stream-ordered, no synchronisation. */
+int pcm_dense_transform(const void *X, int dtype, int64_t n, int d, const void *C, int k, void *out, void *stream);
 
 #ifdef __cplusplus
 }
