@@ -17,6 +17,8 @@ KMeans.predict / transform / fit_transform / score     -> sklearn's API for appl
 dense_predict / dense_transform                        -> generic-D E-step and (n, K) distances for given centres
 kmeans_fuse(clouds, n_clusters, ...)                   -> napari layer tuples
 kmeans_assign(clouds, model)                           -> a later day's cloud labelled against a fused model
+cluster_stats(X, labels, n_clusters, groups=...)       -> ClusterStats: exact per-(day, cluster) counts, sums, second moments
+surface_elements(stats)                                -> per-cluster normal, roughness, planarity, rms (host, from the moments)
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -26,7 +28,8 @@ from .lloyd import LloydResult, lloyd_fit  # noqa: F401
 __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fuse", "HeightMapExtractor",
            "build_library", "kmeans_plusplus", "assemble_cloud", "KMeans", "dense_fit", "dense_kmeanspp",
            "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
-           "dense_transform", "DensePrediction", "kmeans_assign"]
+           "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
+           "SurfaceElements"]
 
 
 def __getattr__(name):
@@ -40,6 +43,9 @@ def __getattr__(name):
     if name in ("lloyd_predict", "LloydPrediction"):
         from . import predict
         return getattr(predict, name)
+    if name in ("cluster_stats", "ClusterStats", "surface_elements", "SurfaceElements"):
+        from . import stats
+        return getattr(stats, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

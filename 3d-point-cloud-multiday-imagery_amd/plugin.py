@@ -44,6 +44,8 @@ try:  # inside the reference tree: the real plugin ABC
 except Exception:  # headless / tests
     from ._interface import SatellitePlugin
 
+from .fixed import fixed_q
+
 PREFIX = "[Multi-day 3D Point Cloud]"
 CLOUD_LAYER_SUFFIX = "3D Point Cloud"
 DEFAULTS = dict(is_debug_mode=True, is_debug_pair=False, is_one_random_pair=True, n=10)
@@ -109,9 +111,34 @@ def load_fused(path) -> dict:
         return {k: f[k] for k in f.files}
 
 
+def _gpu_stats(X, labels: np.ndarray, groups: np.ndarray, k: int, n_groups: int) -> np.ndarray:
+    """X: host (N, 3) float32 array, or the cloud already on the device -> the words (G, K, 16) as NumPy,
+    formed with the exponents ``fixed_q(max|X|)`` of that cloud."""
+    import torch
+
+    from .stats import cluster_stats
+
+    with _gpu_lock:
+        Xt = X.to(torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+        q = fixed_q(Xt.abs().amax(0).cpu().numpy())
+        st = cluster_stats(Xt, torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(Xt.device), k,
+                           groups=torch.from_numpy(np.ascontiguousarray(groups, dtype=np.uint8)).to(Xt.device),
+                           n_groups=n_groups, q=q)
+        return st.numpy()
+
+
+def _describe(X: np.ndarray, labels: np.ndarray, sizes, k: int, Xdev, stats: Optional[Callable]):
+    """The exact per-(cloud, cluster) moments of the labelled cloud (``stats.ClusterStats`` on host words)."""
+    from .stats import ClusterStats
+    groups = np.repeat(np.arange(len(sizes), dtype=np.uint8), sizes)
+    words = (stats or _gpu_stats)(Xdev, np.asarray(labels, dtype=np.int32), groups, k, len(sizes))
+    return ClusterStats(np.asarray(words), fixed_q(np.abs(X).max(axis=0)), 3)
+
+
 def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                 seed: int = 1, fit: Optional[Callable] = None, init: str = "rows", device_clouds=None,
-                export_path=None):
+                export_path=None, describe: bool = False, stats: Optional[Callable] = None):
     """Fuse per-pair (M_i, 3) z,y,x clouds into one K-means reconstruction.
 
     Returns (layers, result) where ``result`` has labels (N,), centers (K, 3),
@@ -121,10 +148,22 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     K is clipped to N.  ``device_clouds``: the same clouds already on the GPU
     (the plugin's GPU assembly) -- the K-means reads them there.  ``export_path``:
     also write the fused cloud (``export_fused``).
+
+    ``describe=True`` adds one exact statistics pass over the labelled cloud
+    (``cluster_stats``; the group of a point is the index of its cloud among the
+    non-empty ``clouds``, at most 256): the centroid layer gains ``roughness``
+    (spread along the element's normal, NaN below 3 points), ``normal_z`` (the z
+    component of the unit normal, >= 0), ``days_seen`` (clouds with a point on the
+    element) and ``height_spread`` (max - min over those clouds of the cloud's
+    mean z on the element, 0 with fewer than two); ``result`` gains ``stats`` =
+    dict(words (G, K, 16) int64, q, sizes).  ``stats`` lets tests substitute
+    (X, labels, groups, k, G) -> words.
     """
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to fuse")
+    if describe and len(clouds) > 256:
+        raise ValueError(f"describe=True takes at most 256 clouds (groups), got {len(clouds)}")
     X = np.concatenate(clouds).astype(np.float32)          # boundary cast (SURVEY.md a4)
     Xfit = X
     if device_clouds is not None and fit is None:
@@ -140,10 +179,23 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
         raise ValueError(f"init must be 'rows' or 'k-means++', got {init!r}")
     labels, centers, inertia, n_iter = (fit or _gpu_fit)(Xfit, C0, int(max_iter), _tolerance(X, tol))
     counts = np.bincount(labels, minlength=k)
+    cprops = {"height": _norm(centers[:, 0].astype(np.float64)), "count": counts}
+    st = None
+    if describe:
+        from .stats import surface_elements
+        sizes = [c.shape[0] for c in clouds]
+        st = _describe(X, labels, sizes, k, Xfit if (stats is None and Xfit is not X) else X, stats)
+        se = surface_elements(st)
+        present = st.counts() > 0                                   # (G, K)
+        mz = np.where(present, st.means()[..., 0], np.nan)
+        with np.errstate(invalid="ignore"):
+            spread = np.where(present.sum(0) >= 2, np.fmax.reduce(mz, axis=0) - np.fmin.reduce(mz, axis=0), 0.0)
+        cprops.update(roughness=se.roughness, normal_z=se.normal[:, 0], days_seen=present.sum(0).astype(np.int64),
+                      height_spread=np.nan_to_num(spread, nan=0.0))
     layers = [
         (centers.astype(np.float64),
          {"name": f"{PREFIX} Fused K-means Centroids", "size": 4,
-          "properties": {"height": _norm(centers[:, 0].astype(np.float64)), "count": counts},
+          "properties": cprops,
           "scale": (1, 1, 1), "opacity": 1.0, "face_colormap": "turbo", "face_color": "height"},
          "points"),
         (X.astype(np.float64),
@@ -153,6 +205,8 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
          "points"),
     ]
     result = dict(labels=labels, centers=centers, inertia=inertia, n_iter=n_iter, n_points=n)
+    if st is not None:
+        result["stats"] = dict(words=st.numpy(), q=list(st.q), sizes=sizes)
     if export_path is not None:
         export_fused(export_path, X.astype(np.float64), result)
     return layers, result
@@ -173,7 +227,8 @@ def _gpu_assign(X, C: np.ndarray):
         return res.labels.cpu().numpy(), res.distance.cpu().numpy(), float(res.inertia)
 
 
-def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None):
+def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None,
+                  describe: bool = False, stats: Optional[Callable] = None):
     """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
 
     ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
@@ -184,6 +239,13 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     distance (= residual), inertia, n_points.  Same boundary cast (float64 ->
     float32) and ``device_clouds`` shortcut as ``kmeans_fuse``; ``assign`` lets
     tests substitute (X, C) -> (labels, squared distances, inertia).
+
+    ``describe=True`` appends a second points layer ``"... Surface Change"``: the
+    model's centres with ``count`` (assigned points), ``dz`` (mean z of the
+    assigned points minus the centre's z, 0 where none) and ``rms`` (rms distance
+    of the assigned points to their mean, 0 where none), from one exact
+    ``cluster_stats`` pass; ``result`` gains ``stats`` = dict(words (1, K, 16), q,
+    sizes).  ``stats``: the test stand-in of ``kmeans_fuse``.
     """
     if not isinstance(model, dict):
         model = load_fused(model)
@@ -208,7 +270,21 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
           "scale": (1, 1, 1), "opacity": 0.8, "face_colormap": "turbo", "face_color": "cluster"},
          "points"),
     ]
-    return layers, dict(labels=labels, distance=residual, inertia=float(inertia), n_points=X.shape[0])
+    result = dict(labels=labels, distance=residual, inertia=float(inertia), n_points=X.shape[0])
+    if describe:
+        k = C.shape[0]
+        st = _describe(X, labels, [X.shape[0]], k, Xq if (stats is None and Xq is not X) else X, stats)
+        cnt = st.counts()[0]
+        dz = np.nan_to_num(st.offsets(C)[0, :, 0], nan=0.0)                                        # NaN: no point
+        rms = np.nan_to_num(np.sqrt(np.maximum(np.trace(st.covariances()[0], axis1=1, axis2=2), 0.0)), nan=0.0)
+        layers.append(
+            (C.astype(np.float64),
+             {"name": f"{PREFIX} Surface Change", "size": 4,
+              "properties": {"count": cnt, "dz": dz, "rms": rms},
+              "scale": (1, 1, 1), "opacity": 1.0, "face_colormap": "turbo", "face_color": "dz"},
+             "points"))
+        result["stats"] = dict(words=st.numpy(), q=list(st.q), sizes=[X.shape[0]])
+    return layers, result
 
 
 class HeightMapExtractor(SatellitePlugin):
@@ -219,12 +295,15 @@ class HeightMapExtractor(SatellitePlugin):
     def __init__(self, base=None, n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                  fit: Optional[Callable] = None, init: str = "rows", seed: int = 1, stages=None,
                  export_path=None, _assemble: Optional[Callable] = None, model=None,
-                 assign: Optional[Callable] = None):
+                 assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None):
         self._base = base
         # model: a fitted model (kmeans_fuse result, load_fused dict or export_fused path); when given,
         # run fuses nothing and labels the run's clouds against it (kmeans_assign)
         self.model = model
         self._assign = assign
+        # describe: add the per-element statistics (kmeans_fuse / kmeans_assign describe=True); stats: test stand-in
+        self.describe = describe
+        self._stats = stats
         self._stages = stages
         self.export_path = export_path
         self._assemble = _assemble   # tests: a CPU stand-in for the GPU assembly (disparity, validity) -> (pts, h_norm)
@@ -262,13 +341,15 @@ class HeightMapExtractor(SatellitePlugin):
         if self.model is not None:
             use_dev = self._assign is None and all(d is not None for d in dev_clouds)
             assigned, self.last_result = kmeans_assign(host_clouds, self.model, assign=self._assign,
-                                                       device_clouds=dev_clouds if use_dev else None)
+                                                       device_clouds=dev_clouds if use_dev else None,
+                                                       describe=self.describe, stats=self._stats)
             return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                               fit=self._fit, init=self.init,
                                               device_clouds=dev_clouds if use_dev else None,
-                                              export_path=self.export_path)
+                                              export_path=self.export_path, describe=self.describe,
+                                              stats=self._stats)
         return layers + fused
 
     def _stages_run(self, kml_path, is_debug_mode, is_debug_pair, is_one_random_pair, n) -> List:
@@ -304,10 +385,12 @@ class HeightMapExtractor(SatellitePlugin):
             if not clouds:   # the pipeline returned only images (or an error layer): pass it through
                 return layers
             if self.model is not None:
-                assigned, self.last_result = kmeans_assign(clouds, self.model, assign=self._assign)
+                assigned, self.last_result = kmeans_assign(clouds, self.model, assign=self._assign,
+                                                           describe=self.describe, stats=self._stats)
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
-                                                  fit=self._fit, init=self.init, export_path=self.export_path)
+                                                  fit=self._fit, init=self.init, export_path=self.export_path,
+                                                  describe=self.describe, stats=self._stats)
             return layers + fused
         except Exception as e:   # reference convention: an error layer, never an exception
             import traceback

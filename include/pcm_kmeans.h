@@ -258,6 +258,43 @@ int pcm_predict_workspace(int64_t n, int d, int k, size_t *bytes);
 int pcm_predict(const void *X, int dtype, int64_t n, int d, const float *C, int k, const int32_t *q, int32_t *labels,
                 float *dist, pcm_inertia *inertia, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------- cluster statistics
+ * Exact per-(group, cluster) zeroth, first and second moments of a labelled
+ * cloud, in one pass over the rows in the caller's order (no reference
+ * counterpart: the reference never fuses days; DESIGN.md §4 "Cluster
+ * statistics").  X: device n*d rows (PCM_F32 or PCM_F16, d = 1..4); labels:
+ * device int32[n] (e.g. of pcm_labels / pcm_predict); groups (nullable: every
+ * row in group 0): device uint8[n], the day / cloud of each row; q: host
+ * int32[d], the fixed-point exponents of the fit (fixed.fixed_q).
+ * With xq_a = trunc(ldexp(x_a, q_a)) (the engine's fixed point), the row of
+ * (g, j) at out + (g*k + j)*W, W = PCM_STATS_WORDS(d), holds
+ *   word 0         the number of rows;
+ *   words 1..d     sum xq_a (int64 two's complement);
+ *   then for each pair a <= b (upper triangle, row-major) two words: with the
+ *   int64 product p = xq_a*xq_b (|p| < 2^50)
+ *       lo += (uint64)p & 0xffffffff,  hi += (uint64)(p >> 32)  (arithmetic
+ *   shift, wrapping add); the pair's value is lo + 2^32 * (int64)hi.
+ * The sums are EXACT while fewer than 2^31 rows in total have been accumulated
+ * into one `out` (over all calls and ranks that were added into it): lo then
+ * stays below 2^63 and |hi| below 2^49.  Every add is an integer add, so the
+ * words are the same bit pattern for any order of the rows, any grid, and any
+ * split of the rows over calls or ranks (sum the words).
+ * A row whose label is outside [0, k), whose group is >= n_groups or which has
+ * a non-finite coordinate is skipped: it adds nothing to any row and 1 to the
+ * trailing word out[n_groups*k*W].
+ * out: device uint64[n_groups*k*W + 1], ACCUMULATED -- the caller zeroes it.
+ * Stream-ordered: no host synchronisation, no allocation.  The arguments are
+ * checked before any device call (PCM_E_ARG: d, dtype, n < 0, n >= 2^31,
+ * k < 1, n_groups outside 1..PCM_STATS_MAXG, n_groups*k >= 2^31, a null out,
+ * labels, X or q with n > 0); n = 0 succeeds without any device call. */
+#define PCM_STATS_WORDS(d) (1 + (d) + (d) * ((d) + 1))      /* D=3: 16 words = 128 B */
+#define PCM_STATS_MAXG 256
+int pcm_cluster_stats(const void *X, int dtype, int64_t n, int d,
+                      const int32_t *labels, const uint8_t *groups /* nullable: all group 0 */,
+                      int n_groups, int k, const int32_t *q /* host int32[d] */,
+                      uint64_t *out /* device, n_groups*k*W + 1 words, ACCUMULATED: caller zeroes */,
+                      void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
