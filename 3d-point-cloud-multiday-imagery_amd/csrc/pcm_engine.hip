@@ -112,7 +112,8 @@ struct pcm_engine {
     double drift_alpha = 2.0, drift_kappa = 0.05;  // candidate-list reuse policy (see k_upd)
     unsigned long long *prev = nullptr;        // raw statistics of the previous iteration
     int iscale = 0;                  // exact-inertia weight exponent (from the global q)
-    unsigned long long *partials = nullptr, *stats = nullptr, *hist_changed = nullptr;
+    unsigned long long *stats = nullptr, *hist_changed = nullptr;
+    unsigned long long *time_sink = nullptr;   // [K][D+1] throw-away target of pcm_time_assign's launches (never read)
     unsigned long long *stats_own = nullptr;   // engine-owned; `stats` may point at a bound buffer
     unsigned long long *held = nullptr;        // statistics of a halted iteration
     double *hist_shift = nullptr;
@@ -451,7 +452,7 @@ int pcm_engine_create(int device, int d, int k, int dtype, int max_iter, pcm_eng
     err = err ? err : hipMalloc(&e->shbuf, (size_t)k * sizeof(double));
     err = err ? err : hipMalloc(&e->upart, (size_t)blocks_for(k, UPD_TPB) * sizeof(UpdPart));
     err = err ? err : hipMalloc(&e->prev, nstat * sizeof(unsigned long long));
-    err = err ? err : hipMalloc(&e->partials, (size_t)2 * k * (d + 1) * sizeof(unsigned long long));
+    err = err ? err : hipMalloc(&e->time_sink, (size_t)k * (d + 1) * sizeof(unsigned long long));
     err = err ? err : hipMalloc(&e->stats_own, nstat * sizeof(unsigned long long));
     e->stats = e->stats_own;
     err = err ? err : hipMalloc(&e->held, nstat * sizeof(unsigned long long));
@@ -468,7 +469,6 @@ int pcm_engine_create(int device, int d, int k, int dtype, int max_iter, pcm_eng
     err = err ? err : hipHostMalloc((void **)&e->ntiles_host, sizeof(uint32_t), hipHostMallocDefault);
     err = err ? err : hipHostMalloc((void **)&e->ctrl_pin, sizeof(Ctrl), hipHostMallocDefault);
     err = err ? err : hipEventCreateWithFlags(&e->st_ev, hipEventDisableTiming);
-    err = err ? err : hipMemset(e->partials, 0, (size_t)2 * k * (d + 1) * sizeof(unsigned long long));
     err = err ? err : hipMemset(e->ctrl, 0, sizeof(Ctrl));
     if (err != hipSuccess) {
         pcm_engine_destroy(e);
@@ -488,7 +488,7 @@ int pcm_engine_destroy(pcm_engine *e) {
         for (int j = 0; j < 4; ++j)
             if (e->ev[i][j]) (void)hipEventDestroy(e->ev[i][j]);
     free_buffers(e);
-    void *ps[] = {e->C, e->Cn, e->cref, e->shbuf, e->upart, e->prev, e->partials, e->stats_own, e->held, e->hist_changed, e->hist_shift, e->ctrl,
+    void *ps[] = {e->C, e->Cn, e->cref, e->shbuf, e->upart, e->prev, e->time_sink, e->stats_own, e->held, e->hist_changed, e->hist_shift, e->ctrl,
                   e->bbox_part, e->nonfinite, e->bbox_out, e->cand_stats, e->rank_buf, e->empty_idx, e->ntiles_dev,
                   e->grows, e->zpts};
     for (void *p : ps)
@@ -894,16 +894,16 @@ int pcm_fit_begin(pcm_engine *e, const float *C0, double tol, int max_iter, void
     HIPCHK(hipMemsetAsync(e->lab, 0xff, (size_t)e->npad * lsize(e), s));   // "no label yet" (-1 / 0xffff)
     // previous raw statistics := 0: iteration 0 "converges" only for an empty cloud,
     // as sklearn's labels-vs-(-1) comparison does
-    {   // prev, partials, stats and the histories := 0 in one launch (five memsets: ~5 us each)
+    {   // prev, stats and the histories := 0 in one launch (four memsets: ~5 us each);
+        // time_sink is never read, so it is not zeroed
         const long long w = (long long)e->k * (e->d + 1);
         ZeroSpans z{};
         z.p[0] = e->prev;         z.n[0] = w + 1;
-        z.p[1] = e->partials;     z.n[1] = 2 * w;
-        z.p[2] = e->stats;        z.n[2] = w + 1;
-        z.p[3] = e->hist_changed; z.n[3] = e->max_iter_cap;
-        z.p[4] = reinterpret_cast<unsigned long long *>(e->hist_shift); z.n[4] = e->max_iter_cap;   // 0.0 = all-zero bits
+        z.p[1] = e->stats;        z.n[1] = w + 1;
+        z.p[2] = e->hist_changed; z.n[2] = e->max_iter_cap;
+        z.p[3] = reinterpret_cast<unsigned long long *>(e->hist_shift); z.n[3] = e->max_iter_cap;   // 0.0 = all-zero bits
         long long tot = 0;
-        for (int q = 0; q < 5; ++q) tot += z.n[q];
+        for (int q = 0; q < 4; ++q) tot += z.n[q];
         k_zero_spans<<<(int)std::min<long long>(1024, (tot + 255) / 256), 256, 0, s>>>(z);
         LAUNCHCHK();
     }
@@ -1061,8 +1061,7 @@ static LloydArgs lloyd_args(pcm_engine *e) {
     A.fc_cnt = e->fc_cnt;
     A.K = e->k;
     for (int a = 0; a < MAXD; ++a) A.q[a] = e->qe.q[a];
-    A.partials = e->partials;
-    A.pstride = (long long)e->k * (e->d + 1);
+    A.stats = e->stats;
     A.ctrl = e->ctrl;
     A.sub_start = e->sub_start;
     A.sub = e->sub;
@@ -1136,20 +1135,16 @@ static int timing_mark(pcm_engine *e, int which, hipStream_t s) {
 }
 
 // k_lloyd (its candidate lists were built by the previous k_lists, the resume
-// path or pcm_fit_begin).  to_stats: accumulate straight into `stats` (the
-// statistics buffer every fit iterates through -- one GPU or the all-reduce /
-// peer-exchange buffer of several -- zeroed by the previous update's
-// publisher, k_global or fit_begin); otherwise into partials[iter & 1], which
-// only the assign-timing calibration (pcm_time_assign) still uses.
-static int iter_local_impl(pcm_engine *e, hipStream_t s, bool to_stats) {
+// path or pcm_fit_begin).  It accumulates into `target`: e->stats in every fit
+// (the statistics buffer -- one GPU or the all-reduce / peer-exchange buffer
+// of several -- zeroed by the previous update, k_resume or fit_begin), or the
+// throw-away e->time_sink of the assign-timing calibration (pcm_time_assign).
+static int iter_local_impl(pcm_engine *e, hipStream_t s, unsigned long long *target) {
     if (int rc = timing_mark(e, 0, s)) return rc;
     if (int rc = launch_tile_lists(e, s, 1)) return rc;   // crowded layouts only
     if (int rc = timing_mark(e, 1, s)) return rc;
     LloydArgs A = lloyd_args(e);
-    if (to_stats) {
-        A.partials = e->stats;
-        A.pstride = 0;
-    }
+    A.stats = target;
     return dispatch_td(e->dtype, e->d, [&](auto T, auto DD) -> int {
         using TT = decltype(T);
         constexpr int D = decltype(DD)::value;
@@ -1182,29 +1177,35 @@ static int iter_local_impl(pcm_engine *e, hipStream_t s, bool to_stats) {
 int pcm_iter_local(pcm_engine *e, void *stream) {
     if (!e) return fail(PCM_E_ARG, "null engine");
     if (!e->fit_ready) return fail(PCM_E_STATE, "pcm_fit_begin must run first");
-    return iter_local_impl(e, (hipStream_t)stream, true);   // into `stats`: the caller all-reduces it
+    return iter_local_impl(e, (hipStream_t)stream, e->stats);   // the caller all-reduces it
 }
 
-// Centre update + next candidate lists.  from_partials = false (every fit): the
-// kernels read `stats` (the summed statistics); true: partials[iter & 1].  Every K: k_upd (the
-// K new centres once, convergence, history) then k_lists (C := new centres,
-// this block's lists rebuilt or refreshed).  The relocation resume takes
-// k_global (it handles `resume`) + k_cand.
-static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bool resume_path) {
+// Centre update + next candidate lists, reading `stats` (the summed statistics)
+// in place.  D <= 3, K <= 1024: k_updlists does both in one launch.  Otherwise
+// k_upd1 (K <= UPD1_MAX) or k_upd (the K new centres once, convergence,
+// history), then k_lists (C := new centres, each block's lists rebuilt or
+// refreshed; D = 4 pruned grids: k_coarse first, then one block per mid cell).
+// The relocation resume takes k_resume + k_cand.
+static int iter_global_impl(pcm_engine *e, hipStream_t s, bool resume_path) {
     int rc = dispatch_d(e->d, [&](auto DD) -> int {
         constexpr int D = decltype(DD)::value;
-        if (!resume_path) {
-            double wmin = 0.0;
-            for (int a = 0; a < D; ++a)
-                if (e->g.ext[a] > 0 && (wmin == 0.0 || e->g.w[a] < wmin)) wmin = e->g.w[a];
-            // D <= 3, K <= 1024: update and lists in one launch (k_updlists)
+        if (resume_path) {
+            k_resume<D><<<1, SHIFT_LANES, 0, s>>>(e->stats, e->k, e->qe, e->C, e->Cn, e->hist_changed, e->hist_shift,
+                                                  e->ctrl);
+            LAUNCHCHK();
+            return launch_candidates(e, s, 1);
+        }
+        double wmin = 0.0;
+        for (int a = 0; a < D; ++a)
+            if (e->g.ext[a] > 0 && (wmin == 0.0 || e->g.w[a] < wmin)) wmin = e->g.w[a];
+        const double dl_cap = e->drift_kappa * wmin;
+        const int bpc = cand_bpc(e);
+        const int nlist = (int)(e->g.ncoarse * bpc);
+        if constexpr (D <= 3) {
             // (PCM_FUSED_UPD=0: k_upd1 + k_lists instead -- A/B and tests; read per
             // launch so tests can switch it between fits, captured graphs keep theirs)
             const char *fz = std::getenv("PCM_FUSED_UPD");
-            const bool fused_on = !(fz && std::atoi(fz) == 0);
-            if (fused_on && D <= 3 && !split_coarse(e) && e->k <= 2 * CAND_TPB) {
-                const int bpc = cand_bpc(e);
-                const int nlist = (int)(e->g.ncoarse * bpc);
+            if (!(fz && std::atoi(fz) == 0) && e->k <= 2 * CAND_TPB) {
                 auto fused = [&](auto RR) {
                     constexpr int RV = decltype(RR)::value;
                     const size_t lds = (size_t)e->k * sizeof(float4);
@@ -1216,38 +1217,37 @@ static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bo
                         hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_updlists<D, RV, true>,
                                                                      CAND_TPB, lds) == hipSuccess &&
                         (long long)nlist + 1 <= (long long)per_cu * e->num_cu;
-                    if (pub)
-                        k_updlists<D, RV, true><<<nlist + 1, CAND_TPB, lds, s>>>(
-                            from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->cref,
-                            e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha, e->drift_kappa * wmin, e->g,
-                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc, sole_args(e));
-                    else
-                        k_updlists<D, RV, false><<<nlist, CAND_TPB, lds, s>>>(
-                            from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->cref,
-                            e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha, e->drift_kappa * wmin, e->g,
-                            e->fc_cnt, e->fc_rec, e->fc_lab, bpc, sole_args(e));
+                    auto kern = pub ? k_updlists<D, RV, true> : k_updlists<D, RV, false>;
+                    kern<<<nlist + (pub ? 1 : 0), CAND_TPB, lds, s>>>(
+                        e->stats, e->k, e->qe, e->held, e->prev, e->C, e->cref, e->hist_changed, e->hist_shift, e->ctrl,
+                        e->drift_alpha, dl_cap, e->g, e->fc_cnt, e->fc_rec, e->fc_lab, bpc, sole_args(e));
                 };
                 if (e->k <= CAND_TPB) fused(std::integral_constant<int, 1>{});
                 else fused(std::integral_constant<int, 2>{});
                 LAUNCHCHK();
                 return 0;
             }
-            // one block (the shift tree in LDS, no hand-off between blocks) up to UPD1_MAX centres
-            auto upd1 = [&](auto RR) {
-                k_upd1<D, decltype(RR)::value><<<1, SHIFT_LANES, 0, s>>>(
-                    from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->Cn,
-                    e->cref, e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha, e->drift_kappa * wmin);
-            };
-            if (e->k <= SHIFT_LANES)
-                upd1(std::integral_constant<int, 1>{});
-            else if (e->k <= UPD1_MAX)
-                upd1(std::integral_constant<int, 2>{});
-            else
-                k_upd<D><<<blocks_for(e->k, UPD_TPB), UPD_TPB, 0, s>>>(
-                    from_partials ? nullptr : e->stats, e->partials, e->k, e->qe, e->held, e->prev, e->C, e->Cn,
-                    e->cref, e->shbuf, e->upart, e->hist_changed, e->hist_shift, e->ctrl, e->drift_alpha,
-                    e->drift_kappa * wmin);
-            LAUNCHCHK();
+        }
+        // one block (the shift tree in LDS, no hand-off between blocks) up to UPD1_MAX centres
+        auto upd1 = [&](auto RR) {
+            k_upd1<D, decltype(RR)::value><<<1, SHIFT_LANES, 0, s>>>(
+                e->stats, e->k, e->qe, e->held, e->prev, e->C, e->Cn, e->cref, e->hist_changed, e->hist_shift, e->ctrl,
+                e->drift_alpha, dl_cap);
+        };
+        if (e->k <= SHIFT_LANES)
+            upd1(std::integral_constant<int, 1>{});
+        else if (e->k <= UPD1_MAX)
+            upd1(std::integral_constant<int, 2>{});
+        else
+            k_upd<D><<<blocks_for(e->k, UPD_TPB), UPD_TPB, 0, s>>>(
+                e->stats, e->k, e->qe, e->held, e->prev, e->C, e->Cn, e->cref, e->shbuf, e->upart, e->hist_changed,
+                e->hist_shift, e->ctrl, e->drift_alpha, dl_cap);
+        LAUNCHCHK();
+        auto lists = [&](auto kern, long long grid, int tpb, size_t lds, int blocks_per_cell, CoarseL cl) {
+            kern<<<(int)grid, tpb, lds, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl, e->fc_cnt, e->fc_rec, e->fc_lab,
+                                             blocks_per_cell, cl, sole_args(e));
+        };
+        if constexpr (D >= 4) {
             if (split_coarse(e)) {
                 if (int rc = ensure_coarse(e)) return rc;
                 k_coarse<D><<<(int)e->g.ncoarse, CAND_TPB, 0, s>>>(e->g, e->Cn, e->k, e->ctrl, 1, e->cl_cnt, e->cl_idx);
@@ -1255,31 +1255,17 @@ static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bo
                 CoarseL cl;
                 cl.in_cnt = e->cl_cnt;
                 cl.in_idx = e->cl_idx;
-                // mid-cell blocks of 256 threads (PCM_LISTS4_TPB=512: the round-4 start's size, A/B only)
-                const char *lt = std::getenv("PCM_LISTS4_TPB");
-                if (lt && std::atoi(lt) == 512)
-                    k_lists<D, 2><<<(int)n_mid(e), CAND_TPB, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
-                                                                      e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl, sole_args(e));
-                else
-                    k_lists<D, 2, false, 256><<<(int)n_mid(e), 256, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
-                                                                             e->fc_cnt, e->fc_rec, e->fc_lab, 1, cl, sole_args(e));
-            } else if (e->k <= LISTS_STAGE_MAX) {   // centres staged in LDS
-                const int bpc = cand_bpc(e);
-                k_lists<D, 4, true><<<(int)(e->g.ncoarse * bpc), CAND_TPB, (size_t)e->k * sizeof(float4), s>>>(
-                    e->g, e->Cn, e->C, e->cref, e->k, e->ctrl, e->fc_cnt, e->fc_rec, e->fc_lab, bpc, CoarseL{}, sole_args(e));
-            } else {
-                const int bpc = cand_bpc(e);
-                k_lists<D><<<(int)(e->g.ncoarse * bpc), CAND_TPB, 0, s>>>(e->g, e->Cn, e->C, e->cref, e->k, e->ctrl,
-                                                                           e->fc_cnt, e->fc_rec, e->fc_lab, bpc,
-                                                                           CoarseL{}, sole_args(e));
+                lists(k_lists<D, 2, false, 256>, n_mid(e), 256, 0, 1, cl);   // mid-cell blocks of 256 threads
+                LAUNCHCHK();
+                return 0;
             }
-            LAUNCHCHK();
-            return 0;
         }
-        k_global<D><<<1, 1024, 0, s>>>(nullptr, e->stats, e->k, e->qe, e->held, e->prev, e->C, e->Cn,
-                                       e->hist_changed, e->hist_shift, e->ctrl);
+        if (e->k <= LISTS_STAGE_MAX)   // centres staged in LDS
+            lists(k_lists<D, 4, true>, nlist, CAND_TPB, (size_t)e->k * sizeof(float4), bpc, CoarseL{});
+        else
+            lists(k_lists<D>, nlist, CAND_TPB, 0, bpc, CoarseL{});
         LAUNCHCHK();
-        return launch_candidates(e, s, 1);
+        return 0;
     });
     if (rc) return rc;
     return timing_mark(e, 3, s);
@@ -1288,7 +1274,7 @@ static int iter_global_impl(pcm_engine *e, hipStream_t s, bool from_partials, bo
 int pcm_iter_global(pcm_engine *e, void *stream) {
     if (!e) return fail(PCM_E_ARG, "null engine");
     if (!e->fit_ready) return fail(PCM_E_STATE, "pcm_fit_begin must run first");
-    return iter_global_impl(e, (hipStream_t)stream, false, false);
+    return iter_global_impl(e, (hipStream_t)stream, false);
 }
 
 int pcm_timing(pcm_engine *e, int enable) {
@@ -1338,8 +1324,8 @@ int pcm_time_assign(pcm_engine *e, int reps, void *stream, double *ms) {
     HIPCHK(hipEventCreate(&g.b));
     HIPCHK(hipEventRecord(g.a, s));
     int rc = 0;
-    for (int i = 0; i < reps && !rc; ++i) rc = iter_local_impl(e, s, false);
-    e->fit_ready = false;   // the partial statistics now hold extra sums
+    for (int i = 0; i < reps && !rc; ++i) rc = iter_local_impl(e, s, e->time_sink);
+    e->fit_ready = false;   // the contract: the fit restarts with pcm_fit_begin
     if (rc) return rc;
     HIPCHK(hipEventRecord(g.b, s));
     HIPCHK(hipEventSynchronize(g.b));
@@ -1351,17 +1337,14 @@ int pcm_time_assign(pcm_engine *e, int reps, void *stream, double *ms) {
 
 // Single-process iterations: the multi-GPU sequence without the all-reduce --
 // k_lloyd1 into the statistics buffer, then the update reading it in place (its
-// publisher zeroes it once every block has read it).  (Round 5 retired the
-// parity halves of `partials` on this path: they made every k_updlists block
-// load both halves, 32 of its 144 B per centroid row; round 6 removed the A/B
-// switch that kept them.)
+// publisher zeroes it once every block has read it).
 int pcm_iterate(pcm_engine *e, int n, void *stream) {
     if (!e || n < 0) return fail(PCM_E_ARG, "bad argument");
     if (!e->fit_ready) return fail(PCM_E_STATE, "pcm_fit_begin must run first");
     hipStream_t s = (hipStream_t)stream;
     for (int i = 0; i < n; ++i) {
-        if (int rc = iter_local_impl(e, s, true)) return rc;
-        if (int rc = iter_global_impl(e, s, false, false)) return rc;
+        if (int rc = iter_local_impl(e, s, e->stats)) return rc;
+        if (int rc = iter_global_impl(e, s, false)) return rc;
     }
     return 0;
 }
@@ -1453,7 +1436,7 @@ int pcm_reloc_apply(pcm_engine *e, const void *records, int n_rec, void *stream)
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(e->stats, e->held, ((size_t)e->k * (e->d + 1) + 1) * sizeof(unsigned long long),
                           hipMemcpyDeviceToDevice, s));
-    return iter_global_impl(e, s, false, true);
+    return iter_global_impl(e, s, true);
 }
 
 int pcm_final(pcm_engine *e, void *stream) {

@@ -5,7 +5,8 @@
 //   k_lloyd1           nearest centroid over the cell's candidates + LDS-privatised
 //                      fixed-point accumulation (replaces _k_means_lloyd.pyx:168-218)
 //   k_label            final E-step: labels + inertia (_kmeans.py:736-750)
-//   k_global           averaging / shift / convergence (_k_means_common.pyx:274-311,
+//   k_upd / k_upd1 / k_updlists (k_resume after a relocation)
+//                      averaging / shift / convergence (_k_means_common.pyx:274-311,
 //                      _kmeans.py:717-732)
 // Layout (once per cloud): k_bbox*, the record sort of pcm_sort.hpp (cell
 // order, AoSoA-4), k_cell_starts_xs, k_tiles.
@@ -209,13 +210,13 @@ template <> __device__ __forceinline__ float to_f<__half>(__half v) { return __h
 
 // Up to 5 buffers of 64-bit words := 0 in one launch (pcm_fit_begin).
 struct ZeroSpans {
-    unsigned long long *p[5];
-    long long n[5];
+    unsigned long long *p[4];
+    long long n[4];
 };
 __global__ __launch_bounds__(256) void k_zero_spans(ZeroSpans z) {
     const long long st = (long long)gridDim.x * blockDim.x;
 #pragma unroll
-    for (int q = 0; q < 5; ++q)
+    for (int q = 0; q < 4; ++q)
         for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < z.n[q]; i += st) z.p[q][i] = 0ull;
 }
 
@@ -1560,8 +1561,7 @@ struct LloydArgs {
     const float4 *C;                // all centres (FULL cells)
     int K;
     int q[MAXD];
-    unsigned long long *partials;   // accumulation target: + (iter & 1) * pstride
-    long long pstride;              // K*(D+1): single-GPU parity halves; 0: the all-reduce buffer itself
+    unsigned long long *stats;      // accumulation target: [K][D+1] integer statistics
     const Ctrl *ctrl;
     const uint32_t *sub_start;      // [(ncells << D) + 1] sub-cell starts (k_lloyd1's per-round candidate masks)
     int sub;                        // the layout is sorted by sub-cell (else sub_start is [ncells + 1])
@@ -1739,7 +1739,7 @@ __global__ __launch_bounds__(TPB) void k_label(LloydArgs A, void *lab, unsigned 
 // with update_centers=True, _k_means_lloyd.pyx:23-165).  It streams ONLY the
 // points (12 B/pt at fp32 D=3): no label array is read or written.  sklearn's
 // strict-convergence test (labels equal, _kmeans.py:717-723) is replaced by
-// "the raw integer statistics equal the previous iteration's" in k_global: equal
+// "the raw integer statistics equal the previous iteration's" in the update kernels (upd_row): equal
 // labels give equal statistics, and equal statistics give equal centres, i.e.
 // shift 0 <= tol, so sklearn stops at that same iteration either way (DESIGN.md
 // "Convergence").
@@ -1870,7 +1870,6 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     uint4 tr = tiles[t];
     unsigned nt = *A.ntiles;
     unsigned gate = A.ctrl->halt | A.ctrl->done;
-    unsigned par = A.ctrl->iter & 1u;
     // the tile's layout-time sums (uniform: scalar loads beside the record's): used
     // only when the owner word is set, loaded here so that such a tile costs one
     // latency in all
@@ -1880,7 +1879,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     constexpr bool ZOK = sizeof(T) == 4 && D == 3;   // compressed tiles exist only for fp32 D = 3
     uint4 zm = make_uint4(0u, 0u, 0u, 0u);
     if (ZOK && A.tmeta) zm = A.tmeta[t];
-    asm volatile("" : "+s"(tr.x), "+s"(tr.y), "+s"(tr.z), "+s"(tr.w), "+s"(nt), "+s"(gate), "+s"(par));   // keep the loads above the exits
+    asm volatile("" : "+s"(tr.x), "+s"(tr.y), "+s"(tr.z), "+s"(tr.w), "+s"(nt), "+s"(gate));   // keep the loads above the exits
     asm volatile("" : "+s"(zm.x), "+s"(zm.y), "+s"(zm.z), "+s"(zm.w));
 #pragma unroll
     for (int a = 0; a < D; ++a) asm volatile("" : "+s"(ts[a]));
@@ -1893,7 +1892,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
         DBG_LV(7, 1ull | ((unsigned long long)(end - start) << 16));
         DBG_L(1);
         DBG_L(2);
-        unsigned long long *pp = A.partials + (size_t)par * A.pstride + (size_t)(tr.w - 1u) * (D + 1);
+        unsigned long long *pp = A.stats + (size_t)(tr.w - 1u) * (D + 1);
         unsigned long long v = (unsigned long long)(end - start);
 #pragma unroll
         for (int a = 0; a < D; ++a) v = tid == a ? (unsigned long long)ts[a] : v;
@@ -2001,7 +2000,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
             for (int j = tid; j < mm * (D + 1); j += TPB) govf[j] = 0ull;
     }
     uint32_t *const myacc = acc + (tid & (AW - 1));
-    unsigned long long *prep = A.partials + (size_t)par * A.pstride;
+    unsigned long long *prep = A.stats;
     __syncthreads();
     if constexpr (CROWD) {
         if (chunked) {   // block-uniform
@@ -2334,192 +2333,20 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     }
 }
 
-// Single block of 1024 threads.  Optionally first folds partials[parity] into
-// `stats` (single-GPU path: no all-reduce in between).  Then
-// reads the (all-reduced) statistics, halts for relocation when a cluster is
-// empty (unless resuming), otherwise averages, computes the shift with the
-// fixed reduction tree (per-thread sums over j = tid + 1024 r, then the halving
-// tree 512..1, as oracle/lloyd_ref.py shift_total) and sets convergence flags.
-template <int D>
-__global__ __launch_bounds__(1024) void k_global(unsigned long long *__restrict__ partials,
-                                                 unsigned long long *__restrict__ stats, int K, QExp qe,
-                                                 unsigned long long *__restrict__ held,
-                                                 unsigned long long *__restrict__ prev,
-                                                 float4 *__restrict__ C, float4 *__restrict__ Cn,
-                                                 unsigned long long *__restrict__ hist_changed,
-                                                 double *__restrict__ hist_shift, Ctrl *__restrict__ ctrl) {
-    if (gated(ctrl)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int *q = qe.q;
-    const int n = K * (D + 1);
-    __shared__ unsigned cnt_empty;
-    __shared__ unsigned long long neq_s;
-    __shared__ unsigned long long wmax[16];
-    __shared__ int warg[16];
-    __shared__ double ssum[1024];
-    if (tid == 0) { cnt_empty = 0; neq_s = 0ull; }
-    __syncthreads();
-    const uint32_t resume = ctrl->resume;
-    // Thread tid owns centroids j = tid + 1024 r: every load of a row (and of
-    // the previous statistics) is issued before any is consumed, so a pass
-    // costs one memory round trip.
-    // Convergence (sklearn: labels equal, _kmeans.py:717-723): the raw statistics
-    // of this iteration (before any relocation move) equal the previous ones.
-    unsigned long long neq = 0, bmax = 0;
-    int barg = 0x7fffffff;
-    unsigned ne = 0;
-    for (int j = tid; j < K; j += 1024) {
-        unsigned long long row[D + 1], pv[D + 1];
-        const size_t o = (size_t)j * (D + 1);
-        if (partials) {
-            unsigned long long *src = partials + (size_t)(ctrl->iter & 1u) * n;
-#pragma unroll
-            for (int a = 0; a <= D; ++a) { row[a] = src[o + a]; pv[a] = prev[o + a]; }
-#pragma unroll
-            for (int a = 0; a <= D; ++a) {
-                src[o + a] = 0ull;
-                stats[o + a] = row[a];
-            }
-        } else {
-#pragma unroll
-            for (int a = 0; a <= D; ++a) { row[a] = stats[o + a]; pv[a] = prev[o + a]; }
-        }
-        if (!resume) {
-#pragma unroll
-            for (int a = 0; a <= D; ++a) {
-                neq += (row[a] != pv[a]) ? 1ull : 0ull;
-                prev[o + a] = row[a];
-            }
-        }
-        const unsigned long long c = row[D];
-        if (c == 0) ne++;
-        if (c > bmax) { bmax = c; barg = j; }
-    }
-    if (partials && tid == 0) stats[n] = 0ull;
-    if (neq) atomicAdd(&neq_s, neq);
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long ob = __shfl_xor(bmax, o);
-        const int oa = __shfl_xor(barg, o);
-        if (ob > bmax || (ob == bmax && oa < barg)) { bmax = ob; barg = oa; }
-    }
-    if (lane == 0) { wmax[wv] = bmax; warg[wv] = barg; }
-    if (ne) atomicAdd(&cnt_empty, ne);
-    __syncthreads();
-    if (cnt_empty > 0 && !resume) {
-        // Snapshot the reduced statistics: the no-op iterations queued behind a
-        // halt still run their all-reduce on `stats`.
-        for (int i = tid; i < n + 1; i += 1024) held[i] = stats[i];
-        if (tid == 0) {
-            ctrl->halt = 1u;
-            ctrl->n_empty = cnt_empty;
-            ctrl->neq_saved = neq_s;
-        }
-        return;
-    }
-    unsigned long long gmax = wmax[0];
-    int argmax = warg[0];
-    for (int w = 1; w < 16; ++w)
-        if (wmax[w] > gmax || (wmax[w] == gmax && warg[w] < argmax)) { gmax = wmax[w]; argmax = warg[w]; }
-    // average + shift (thread tid owns j = tid + 1024 r in every loop below);
-    // shift: per-thread sequential sum over its j, then the fixed tree below
-    auto average_row = [&](int j, float4 &cn) -> bool {
-        unsigned long long row[D + 1];
-#pragma unroll
-        for (int a = 0; a <= D; ++a) row[a] = stats[(size_t)j * (D + 1) + a];
-        const unsigned long long c = row[D];
-        float out[4] = {0.f, 0.f, 0.f, 0.f};
-        if (c > 0) {
-#pragma unroll
-            for (int a = 0; a < D; ++a) {
-                const long long sv = (long long)row[a];   // exact signed sum
-                const double m = ((double)sv * __builtin_ldexp(1.0, -q[a])) / (double)c;
-                out[a] = (float)m;
-            }
-        }
-        cn = make_float4(out[0], out[1], out[2], out[3]);
-        return c > 0;
-    };
-    auto shift_of = [&](const float4 &a4, const float4 &b4) -> double {
-        double sh = 0.0;
-#pragma unroll
-        for (int a = 0; a < D; ++a) {
-            const double dd = (double)comp(a4, a) - (double)comp(b4, a);
-            const double sq = dd * dd;
-            sh = (a == 0) ? sq : sh + sq;
-        }
-        return sh;
-    };
-    double acc = 0.0;
-    if (cnt_empty == 0) {   // the common case: no empty cluster, one pass
-        for (int j = tid; j < K; j += 1024) {
-            const float4 b4 = C[j];
-            float4 cn;
-            average_row(j, cn);
-            acc = acc + shift_of(cn, b4);
-            C[j] = cn;
-        }
-    } else {   // resumed after relocation: an empty cluster copies the largest one's centre
-        for (int j = tid; j < K; j += 1024) {
-            float4 cn;
-            if (average_row(j, cn)) Cn[j] = cn;
-        }
-        __syncthreads();   // Cn[argmax] is read by other threads
-        for (int j = tid; j < K; j += 1024) {
-            const unsigned long long c = stats[(size_t)j * (D + 1) + D];
-            if (c == 0) Cn[j] = (gmax > 0) ? Cn[argmax] : C[j];
-            const float4 a4 = Cn[j], b4 = C[j];
-            acc = acc + shift_of(a4, b4);
-            C[j] = Cn[j];
-        }
-    }
-    ssum[tid] = acc;
-    __syncthreads();
-    // statistics read in place (all-reduce buffer / resume): zero them for the
-    // next iteration's accumulation (every read above precedes the barrier)
-    if (!partials)
-        for (int i = tid; i < n + 1; i += 1024) stats[i] = 0ull;
-    for (int st = 512; st >= 64; st >>= 1) {
-        if (tid < st) ssum[tid] = ssum[tid] + ssum[tid + st];
-        __syncthreads();
-    }
-    if (wv == 0) {
-        double v = ssum[lane];
-        for (int st = 32; st > 0; st >>= 1) v = v + __shfl_down(v, st);   // lane t: v_t + v_{t+st}
-        if (lane == 0) {
-            const unsigned long long changed = resume ? ctrl->neq_saved : neq_s;
-            const double shift = v;
-            const uint32_t it = ctrl->iter;
-            if (it < ctrl->max_iter) {
-                hist_changed[it] = changed;
-                hist_shift[it] = shift;
-            }
-            ctrl->last_changed = changed;
-            ctrl->last_shift = shift;
-            ctrl->resume = 0u;
-            uint32_t done = 0;
-            if (changed == 0ull) done = 1u;
-            else if (shift <= ctrl->tol) done = 2u;
-            ctrl->iter = it + 1;
-            if (!done && it + 1 >= ctrl->max_iter) done = 3u;
-            ctrl->done = done;
-        }
-    }
-}
-
 // ------------------------------------------------------------------ centre update + candidate lists
 // One Lloyd iteration's M-step (_average_centers, _center_shift, the
 // convergence tests; _k_means_common.pyx:274-311, _kmeans.py:717-732) and the
 // next iteration's candidate lists, in two launches:
 //
-//  k_upd   one thread per centroid: its row of the (all-reduced) integer
-//          statistics -> the new centre Cn[j] (computed ONCE per iteration),
-//          the statistics-equality test against the previous iteration, the
-//          relocation snapshot `held`, zeroing of the next accumulation target,
-//          its squared shift sh[j] and drift from the lists' reference centre.
-//          Block sums/maxima go to ctrl by agent-scope atomics; the last block
+//  k_upd   one thread per centroid: its row of `stats` (the summed integer
+//          statistics, read and zeroed in place) -> the new centre Cn[j]
+//          (computed ONCE per iteration), the statistics-equality test against
+//          the previous iteration, the relocation snapshot `held`, its squared
+//          shift sh[j] and drift from the lists' reference centre.  Each block
+//          leaves a record (UpdPart); the last block
 //          to arrive reduces the shift with the fixed 1024-lane tree of
 //          oracle/lloyd_ref.py shift_total, halts on an empty cluster (the host
-//          relocates, then k_global + k_cand resume), or publishes the history,
+//          relocates, then k_resume + k_cand resume), or publishes the history,
 //          flags and the list work: REFRESH the lists' records when every
 //          centre is still within the lists' drift budget of the reference
 //          position they were built at (the lists stay exact, see prunable),
@@ -2554,14 +2381,42 @@ __device__ __forceinline__ void upd_load(int j, int K, const unsigned long long 
     rj = cref[(size_t)sel * K + j];
     oj = C[j];
 }
-// its new centre (_average_centers: one fp64 division, one rounding to fp32),
-// changed statistic words, emptiness, squared drift and squared shift
-template <int D>
-__device__ __forceinline__ void upd_row(const unsigned long long (&row)[D + 1], const unsigned long long (&pv)[D + 1],
-                                        const float4 &rj, const float4 &oj, const QExp &qe, float4 &cnew,
-                                        unsigned long long &neq, unsigned &ne, double &dr, double &ds) {
+// the rows of thread tid, centroid j = tid + S r (k_upd1, k_updlists): statistics,
+// previous statistics, BOTH reference buffers (selected once ref_sel is in,
+// instead of a second dependent round) and the old centre.  Called before the
+// gate test, so every load of the launch shares one memory latency with the
+// control words.
+template <int D, int R, int S>
+__device__ __forceinline__ void upd_load_rows(int tid, int K, const unsigned long long *stats,
+                                              const unsigned long long *prev, const float4 *cref, const float4 *C,
+                                              unsigned long long (&row)[R][D + 1], unsigned long long (&pv)[R][D + 1],
+                                              float4 (&rj)[R], float4 (&rk)[R], float4 (&oj)[R]) {
 #pragma unroll
-    for (int a = 0; a <= D; ++a) neq += (row[a] != pv[a]) ? 1ull : 0ull;   // raw statistics vs the previous ones
+    for (int r = 0; r < R; ++r) {
+        // a thread past K loads centroid 0 (in bounds, unused): without a branch
+        // the loads of every row issue back to back (with one, the compiler
+        // moved the first use into it and waited between the rows)
+        const int j = tid + S * r < K ? tid + S * r : 0;
+        const size_t o = (size_t)j * (D + 1);
+#pragma unroll
+        for (int a = 0; a <= D; ++a) { row[r][a] = stats[o + a]; pv[r][a] = prev[o + a]; }
+        rj[r] = cref[j];
+        rk[r] = cref[(size_t)K + j];
+        oj[r] = C[j];
+    }
+    // keep the loads above the caller's gate test (the compiler otherwise sinks
+    // them below it, behind the control words: a second latency)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+#pragma unroll
+        for (int a = 0; a <= D; ++a) asm volatile("" : "+v"(row[r][a]), "+v"(pv[r][a]));
+        asm volatile("" : "+v"(rj[r].x), "+v"(rk[r].x), "+v"(oj[r].x));
+    }
+}
+// the exact mean of a statistics row (_average_centers: the signed fixed-point
+// sum, one fp64 division, one rounding to fp32); zero for an empty cluster
+template <int D>
+__device__ __forceinline__ float4 row_mean(const unsigned long long (&row)[D + 1], const QExp &qe) {
     const unsigned long long c = row[D];
     float out[4] = {0.f, 0.f, 0.f, 0.f};
     if (c > 0) {
@@ -2570,10 +2425,18 @@ __device__ __forceinline__ void upd_row(const unsigned long long (&row)[D + 1], 
             const double m = ((double)(long long)row[a] * __builtin_ldexp(1.0, -qe.q[a])) / (double)c;
             out[a] = (float)m;
         }
-    } else {
-        ne += 1u;
     }
-    cnew = make_float4(out[0], out[1], out[2], out[3]);
+    return make_float4(out[0], out[1], out[2], out[3]);
+}
+// its new centre, changed statistic words, emptiness, squared drift and squared shift
+template <int D>
+__device__ __forceinline__ void upd_row(const unsigned long long (&row)[D + 1], const unsigned long long (&pv)[D + 1],
+                                        const float4 &rj, const float4 &oj, const QExp &qe, float4 &cnew,
+                                        unsigned long long &neq, unsigned &ne, double &dr, double &ds) {
+#pragma unroll
+    for (int a = 0; a <= D; ++a) neq += (row[a] != pv[a]) ? 1ull : 0ull;   // raw statistics vs the previous ones
+    ne += row[D] == 0ull ? 1u : 0u;
+    cnew = row_mean<D>(row, qe);
 #pragma unroll
     for (int a = 0; a < D; ++a) {
         const double e1 = (double)comp(cnew, a) - (double)comp(rj, a);
@@ -2581,6 +2444,67 @@ __device__ __forceinline__ void upd_row(const unsigned long long (&row)[D + 1], 
         dr += e1 * e1;
         ds += e2 * e2;
     }
+}
+// block reduction of (changed words, empty clusters, max squared drift, max
+// squared shift) over NW waves: upd_wave_sums before a block barrier, upd_block_sums
+// after it (every thread gets the same totals; sums and maxima are order-free)
+template <int NW>
+struct UpdSums {
+    unsigned long long neq[NW];
+    unsigned ne[NW];
+    double dr[NW], ds[NW];
+};
+template <int NW>
+__device__ __forceinline__ void upd_wave_sums(UpdSums<NW> &s, int tid, unsigned long long neq, unsigned ne, double dr,
+                                              double ds) {
+    for (int o = 32; o > 0; o >>= 1) {
+        neq += __shfl_xor(neq, o);
+        ne += __shfl_xor(ne, o);
+        dr = fmax(dr, __shfl_xor(dr, o));
+        ds = fmax(ds, __shfl_xor(ds, o));
+    }
+    if ((tid & 63) == 0) { s.neq[tid >> 6] = neq; s.ne[tid >> 6] = ne; s.dr[tid >> 6] = dr; s.ds[tid >> 6] = ds; }
+}
+template <int NW>
+__device__ __forceinline__ void upd_block_sums(const UpdSums<NW> &s, unsigned long long &changed,
+                                               unsigned long long &n_empty, double &dmax, double &smax) {
+    changed = 0ull; n_empty = 0ull; dmax = 0.0; smax = 0.0;
+    for (int w = 0; w < NW; ++w) {
+        changed += s.neq[w]; n_empty += s.ne[w]; dmax = fmax(dmax, s.dr[w]); smax = fmax(smax, s.ds[w]);
+    }
+}
+// one lane: an empty cluster halts the iteration (the host relocates, then
+// k_resume + k_cand resume)
+__device__ __forceinline__ void upd_halt(Ctrl *ctrl, unsigned long long n_empty, unsigned long long changed) {
+    ctrl->n_empty = (unsigned)n_empty;
+    ctrl->neq_saved = changed;
+    ctrl->lists = 0u;
+    ctrl->halt = 1u;
+}
+// The tail of oracle/lloyd_ref.py shift_total's halving tree (lane L += lane
+// L + h) over the N lanes the block's N threads stored in s[] before a barrier:
+// LDS steps down to 128 lanes, the step h = 64 as they are read, then wave
+// shuffles.  Block-uniform call; every wave computes the same total (no branch:
+// a wave-0-only tail cost the callers a VGPR), valid in its lane 0.
+template <int N>
+__device__ __forceinline__ double shift_tree_tail(double *s, int tid) {
+    for (int h = N / 2; h >= 128; h >>= 1) {
+        if (tid < h) s[tid] = s[tid] + s[tid + h];
+        __syncthreads();
+    }
+    double x = s[tid & 63] + s[(tid & 63) + 64];
+    for (int st = 32; st > 0; st >>= 1) x = x + __shfl_down(x, st);   // lane t: x_t + x_{t+st}
+    return x;
+}
+// rebuild the lists or refresh their records: REFRESH while every centre is
+// within the lists' drift budget of its reference position; a rebuild's new
+// budget is alpha * (largest shift), or 0 above the cap
+constexpr double DRIFT_SLACK = 1.0 + 9.094947017729282e-13;   // 1 + 2^-40: fp64 rounding of the drift norms
+__device__ __forceinline__ void upd_decide(double dmax, double smax, double budget, double alpha, double dl_cap,
+                                           bool &rebuild, double &dl_new) {
+    rebuild = !(sqrt(dmax) * DRIFT_SLACK <= budget);
+    dl_new = alpha * sqrt(smax) * DRIFT_SLACK;
+    if (!(dl_new <= dl_cap)) dl_new = 0.0;
 }
 // one lane: history, convergence flags and the list work of the next launch
 // (it, max_iter, budget, tol: the control words as this launch found them)
@@ -2595,10 +2519,9 @@ __device__ __forceinline__ void upd_publish(Ctrl *ctrl, unsigned long long chang
     ctrl->last_changed = changed;
     ctrl->last_shift = shift;
     ctrl->resume = 0u;
-    const double slack = 1.0 + 9.094947017729282e-13;   // 1 + 2^-40: fp64 rounding of the drift norms
-    const bool rebuild = !(sqrt(dmax) * slack <= budget);
-    double dl_new = alpha * sqrt(smax) * slack;
-    if (!(dl_new <= dl_cap)) dl_new = 0.0;
+    bool rebuild;
+    double dl_new;
+    upd_decide(dmax, smax, budget, alpha, dl_cap, rebuild, dl_new);
     if (rebuild) {
         ctrl->ref_sel = sel ^ 1u;
         ctrl->budget = dl_new;
@@ -2615,8 +2538,7 @@ __device__ __forceinline__ void upd_publish(Ctrl *ctrl, unsigned long long chang
 }
 
 template <int D>
-__global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict__ stats_in,
-                                                 unsigned long long *__restrict__ partials, int K, QExp qe,
+__global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict__ stats, int K, QExp qe,
                                                  unsigned long long *__restrict__ held,
                                                  unsigned long long *__restrict__ prev, const float4 *__restrict__ C,
                                                  float4 *__restrict__ Cn, const float4 *__restrict__ cref,
@@ -2624,16 +2546,14 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
                                                  unsigned long long *__restrict__ hist_changed,
                                                  double *__restrict__ hist_shift, Ctrl *__restrict__ ctrl, double alpha,
                                                  double dl_cap) {
-    // the gate flags and the control words this launch reads, in one memory latency
+    // the gate flags and the control word this launch reads, in one memory latency
     unsigned gate = ctrl->halt | ctrl->done;
-    unsigned par = ctrl->iter & 1u;
     unsigned sel = ctrl->ref_sel;
-    asm volatile("" : "+s"(gate), "+s"(par), "+s"(sel));   // keep the loads above the exit
+    asm volatile("" : "+s"(gate), "+s"(sel));   // keep the loads above the exit
     if (gate != 0u) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int n = K * (D + 1);
     const int j = blockIdx.x * UPD_TPB + tid;
-    unsigned long long *src = stats_in ? stats_in : partials + (size_t)par * n;
     unsigned long long neq = 0ull;
     unsigned ne = 0u;
     double dr = 0.0, ds = 0.0;
@@ -2641,7 +2561,7 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
     float4 rj, oj;
     float4 cnew = make_float4(0.f, 0.f, 0.f, 0.f);
     if (j < K) {
-        upd_load<D>(j, K, src, prev, cref, sel, C, row, pv, rj, oj);
+        upd_load<D>(j, K, stats, prev, cref, sel, C, row, pv, rj, oj);
         upd_row<D>(row, pv, rj, oj, qe, cnew, neq, ne, dr, ds);
         __hip_atomic_store(sh + j, ds, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -2650,42 +2570,33 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (j < K) {
         const size_t o = (size_t)j * (D + 1);
-        unsigned long long *pnext = stats_in ? stats_in : partials + (size_t)(par ^ 1u) * n;
 #pragma unroll
         for (int a = 0; a <= D; ++a) {
             prev[o + a] = row[a];
             held[o + a] = row[a];   // the relocation snapshot, should this iteration halt
-            pnext[o + a] = 0ull;    // the next accumulation starts from zero
+            stats[o + a] = 0ull;    // the next accumulation starts from zero
         }
         Cn[j] = cnew;
     }
     if (j == 0) {
         held[n] = 0ull;
-        if (stats_in) stats_in[n] = 0ull;
+        stats[n] = 0ull;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        neq += __shfl_xor(neq, o);
-        ne += __shfl_xor(ne, o);
-        dr = fmax(dr, __shfl_xor(dr, o));
-        ds = fmax(ds, __shfl_xor(ds, o));
-    }
-    __shared__ unsigned long long s_neq[UPD_TPB / 64];
-    __shared__ unsigned s_ne[UPD_TPB / 64];
-    __shared__ double s_dr[UPD_TPB / 64], s_ds[UPD_TPB / 64];
+    __shared__ UpdSums<UPD_TPB / 64> sums;
     __shared__ unsigned s_last;
-    if (lane == 0) { s_neq[wv] = neq; s_ne[wv] = ne; s_dr[wv] = dr; s_ds[wv] = ds; }
+    unsigned long long changed, n_empty;
+    double dmax, smax;
+    upd_wave_sums(sums, tid, neq, ne, dr, ds);
     __syncthreads();
     if (tid == 0) {
-        for (int w = 1; w < UPD_TPB / 64; ++w) {
-            neq += s_neq[w]; ne += s_ne[w]; dr = fmax(dr, s_dr[w]); ds = fmax(ds, s_ds[w]);
-        }
+        upd_block_sums(sums, changed, n_empty, dmax, smax);
         // this block's record (sc1 stores, drained before the arrival like sh[])
         UpdPart *pp = upart + blockIdx.x;
-        __hip_atomic_store(&pp->neq, neq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&pp->nempty, (unsigned long long)ne, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&pp->dmax_bits, (unsigned long long)__double_as_longlong(dr), __ATOMIC_RELAXED,
+        __hip_atomic_store(&pp->neq, changed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&pp->nempty, n_empty, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&pp->dmax_bits, (unsigned long long)__double_as_longlong(dmax), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(&pp->smax_bits, (unsigned long long)__double_as_longlong(ds), __ATOMIC_RELAXED,
+        __hip_atomic_store(&pp->smax_bits, (unsigned long long)__double_as_longlong(smax), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // release (arrive_last): this block's sh[] and record stores are ordered
@@ -2696,8 +2607,7 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
     if (!s_last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");   // every other block's published stores are visible
     // ---- the last block: every other block's sh[] and record have landed
-    unsigned long long changed = 0ull, n_empty = 0ull;
-    double dmax = 0.0, smax = 0.0;
+    changed = 0ull; n_empty = 0ull; dmax = 0.0; smax = 0.0;
     for (int b = tid; b < (int)gridDim.x; b += UPD_TPB) {
         const UpdPart *pp = upart + b;
         changed += __hip_atomic_load(&pp->neq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2707,30 +2617,13 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
         smax = fmax(smax, __longlong_as_double(
                               (long long)__hip_atomic_load(&pp->smax_bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        changed += __shfl_xor(changed, o);
-        n_empty += __shfl_xor(n_empty, o);
-        dmax = fmax(dmax, __shfl_xor(dmax, o));
-        smax = fmax(smax, __shfl_xor(smax, o));
-    }
-    __syncthreads();   // s_* of the arrival phase are reused below
-    if (lane == 0) { s_neq[wv] = changed; s_ne[wv] = (unsigned)n_empty; s_dr[wv] = dmax; s_ds[wv] = smax; }
+    // (sums of the arrival phase is reused: its readers passed the barrier above)
+    upd_wave_sums(sums, tid, changed, (unsigned)n_empty, dmax, smax);
     __syncthreads();
-    changed = s_neq[0];
-    n_empty = s_ne[0];
-    dmax = s_dr[0];
-    smax = s_ds[0];
-    for (int w = 1; w < UPD_TPB / 64; ++w) {
-        changed += s_neq[w]; n_empty += s_ne[w]; dmax = fmax(dmax, s_dr[w]); smax = fmax(smax, s_ds[w]);
-    }
+    upd_block_sums(sums, changed, n_empty, dmax, smax);
     if (tid == 0) __hip_atomic_store(&ctrl->u_arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (n_empty > 0ull) {   // empty cluster: the host relocates, then k_global + k_cand resume
-        if (tid == 0) {
-            ctrl->n_empty = (unsigned)n_empty;
-            ctrl->neq_saved = changed;
-            ctrl->lists = 0u;
-            ctrl->halt = 1u;
-        }
+    if (n_empty > 0ull) {
+        if (tid == 0) upd_halt(ctrl, n_empty, changed);
         return;
     }
     // total shift: lane L sums sh[L + 1024 r] in ascending r, then the halving tree
@@ -2750,15 +2643,12 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
     __shared__ double s_tree[UPD_TPB];
     s_tree[tid] = v[0];
     __syncthreads();
-    if (wv == 0) {
-        double x = s_tree[lane];
-        x = x + s_tree[lane + 64];
-        for (int st = 32; st > 0; st >>= 1) x = x + __shfl_down(x, st);   // lane t: x_t + x_{t+st}
-        if (lane == 0)
-            upd_publish(ctrl, changed, x, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, ctrl->iter,
-                        ctrl->max_iter, ctrl->budget, ctrl->tol);
-    }
+    const double shift = shift_tree_tail<UPD_TPB>(s_tree, tid);
+    if (tid == 0)
+        upd_publish(ctrl, changed, shift, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, ctrl->iter,
+                    ctrl->max_iter, ctrl->budget, ctrl->tol);
 }
+
 
 // k_upd in ONE block of SHIFT_LANES threads (K <= UPD1_MAX: configs 1-4): thread L owns centroids L + 1024 r, so its tree lane's
 // sum (ascending r) stays in registers and the halving tree runs in LDS -- no
@@ -2770,8 +2660,7 @@ __global__ __launch_bounds__(UPD_TPB) void k_upd(unsigned long long *__restrict_
 // within 128 VGPRs) measured 28 us against k_upd's 15 at an 8-way config-5 slab.
 constexpr int UPD1_MAX = 2 * SHIFT_LANES;
 template <int D, int R>
-__global__ __launch_bounds__(SHIFT_LANES) void k_upd1(unsigned long long *__restrict__ stats_in,
-                                                      unsigned long long *__restrict__ partials, int K, QExp qe,
+__global__ __launch_bounds__(SHIFT_LANES) void k_upd1(unsigned long long *__restrict__ stats, int K, QExp qe,
                                                       unsigned long long *__restrict__ held,
                                                       unsigned long long *__restrict__ prev,
                                                       const float4 *__restrict__ C, float4 *__restrict__ Cn,
@@ -2779,45 +2668,20 @@ __global__ __launch_bounds__(SHIFT_LANES) void k_upd1(unsigned long long *__rest
                                                       unsigned long long *__restrict__ hist_changed,
                                                       double *__restrict__ hist_shift, Ctrl *__restrict__ ctrl,
                                                       double alpha, double dl_cap) {
-    // every load of the launch in ONE memory latency: the control words, the
-    // rows of both parity halves of `partials` and both reference buffers
-    // (selected once the words are in, instead of a second dependent round)
+    // every load of the launch in ONE memory latency: the control words and the rows
     unsigned gate = ctrl->halt | ctrl->done;
-    const uint32_t it = ctrl->iter, max_iter = ctrl->max_iter;
-    const unsigned sel = ctrl->ref_sel;
-    const double budget = ctrl->budget, tol = ctrl->tol;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t it = ctrl->iter, max_iter = ctrl->max_iter;
+    unsigned sel = ctrl->ref_sel;
+    double budget = ctrl->budget, tol = ctrl->tol;
+    const int tid = threadIdx.x;
     const int n = K * (D + 1);
-    // (R > 2: too many registers for both halves -- the rows follow the control
-    // words, one more latency)
     static_assert(R >= 1 && R <= 2, "K <= UPD1_MAX");
-    unsigned long long row[R][D + 1], alt[R][D + 1], pv[R][D + 1];
+    unsigned long long row[R][D + 1], pv[R][D + 1];
     float4 rj[R], rk[R], oj[R];
-    const unsigned par = it & 1u;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int j = tid + SHIFT_LANES * r;
-        if (j < K) {
-            const size_t o = (size_t)j * (D + 1);
-#pragma unroll
-            for (int a = 0; a <= D; ++a) {
-                row[r][a] = stats_in ? stats_in[o + a] : partials[o + a];
-                alt[r][a] = stats_in ? 0ull : partials[(size_t)n + o + a];
-                pv[r][a] = prev[o + a];
-            }
-            rj[r] = cref[j];
-            rk[r] = cref[(size_t)K + j];
-            oj[r] = C[j];
-        }
-    }
+    upd_load_rows<D, R, SHIFT_LANES>(tid, K, stats, prev, cref, C, row, pv, rj, rk, oj);
+    // keep the control-word loads above the exit, in flight with the rows
+    asm volatile("" : "+s"(gate), "+s"(it), "+s"(max_iter), "+s"(sel), "+s"(budget), "+s"(tol));
     if (gate != 0u) return;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!stats_in && par)
-#pragma unroll
-            for (int a = 0; a <= D; ++a) row[r][a] = alt[r][a];
-        if (sel) rj[r] = rk[r];
-    }
     unsigned long long neq = 0ull;
     unsigned ne = 0u;
     double dr = 0.0, ds = 0.0, v = 0.0;
@@ -2827,13 +2691,12 @@ __global__ __launch_bounds__(SHIFT_LANES) void k_upd1(unsigned long long *__rest
         const int j = tid + SHIFT_LANES * r;
         if (j < K) {
             double drj = 0.0, dsj = 0.0;
-            upd_row<D>(row[r], pv[r], rj[r], oj[r], qe, cnew[r], neq, ne, drj, dsj);
+            upd_row<D>(row[r], pv[r], sel ? rk[r] : rj[r], oj[r], qe, cnew[r], neq, ne, drj, dsj);
             dr = fmax(dr, drj);
             ds = fmax(ds, dsj);
             v = v + dsj;   // tree lane tid: sh[tid + 1024 r] in ascending r
         }
     }
-    unsigned long long *pnext = stats_in ? stats_in : partials + (size_t)(par ^ 1u) * n;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int j = tid + SHIFT_LANES * r;
@@ -2843,56 +2706,33 @@ __global__ __launch_bounds__(SHIFT_LANES) void k_upd1(unsigned long long *__rest
             for (int a = 0; a <= D; ++a) {
                 prev[o + a] = row[r][a];
                 held[o + a] = row[r][a];   // the relocation snapshot, should this iteration halt
-                pnext[o + a] = 0ull;       // the next accumulation starts from zero
+                stats[o + a] = 0ull;       // the next accumulation starts from zero
             }
             Cn[j] = cnew[r];
         }
     }
     if (tid == 0) {
         held[n] = 0ull;
-        if (stats_in) stats_in[n] = 0ull;
+        stats[n] = 0ull;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        neq += __shfl_xor(neq, o);
-        ne += __shfl_xor(ne, o);
-        dr = fmax(dr, __shfl_xor(dr, o));
-        ds = fmax(ds, __shfl_xor(ds, o));
-    }
-    constexpr int NW = SHIFT_LANES / 64;
-    __shared__ unsigned long long s_neq[NW];
-    __shared__ unsigned s_ne[NW];
-    __shared__ double s_dr[NW], s_ds[NW];
+    __shared__ UpdSums<SHIFT_LANES / 64> sums;
     __shared__ double s_tree[SHIFT_LANES];
-    if (lane == 0) { s_neq[wv] = neq; s_ne[wv] = ne; s_dr[wv] = dr; s_ds[wv] = ds; }
+    upd_wave_sums(sums, tid, neq, ne, dr, ds);
     s_tree[tid] = v;
     __syncthreads();
-    unsigned long long changed = 0ull, n_empty = 0ull;
-    double dmax = 0.0, smax = 0.0;
-    for (int w = 0; w < NW; ++w) {
-        changed += s_neq[w]; n_empty += s_ne[w]; dmax = fmax(dmax, s_dr[w]); smax = fmax(smax, s_ds[w]);
-    }
-    if (n_empty > 0ull) {   // empty cluster: the host relocates, then k_global + k_cand resume
-        if (tid == 0) {
-            ctrl->n_empty = (unsigned)n_empty;
-            ctrl->neq_saved = changed;
-            ctrl->lists = 0u;
-            ctrl->halt = 1u;
-        }
+    unsigned long long changed, n_empty;
+    double dmax, smax;
+    upd_block_sums(sums, changed, n_empty, dmax, smax);
+    if (n_empty > 0ull) {
+        if (tid == 0) upd_halt(ctrl, n_empty, changed);
         return;
     }
-    // the halving tree of oracle/lloyd_ref.py shift_total: lane L += lane L + h
-    for (int h = SHIFT_LANES / 2; h >= 64; h >>= 1) {
-        if (tid < h) s_tree[tid] = s_tree[tid] + s_tree[tid + h];
-        __syncthreads();
-    }
-    if (wv == 0) {
-        double x = s_tree[lane];
-        for (int st = 32; st > 0; st >>= 1) x = x + __shfl_down(x, st);   // lane t: x_t + x_{t+st}
-        if (lane == 0)
-            upd_publish(ctrl, changed, x, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, it, max_iter,
-                        budget, tol);
-    }
+    const double shift = shift_tree_tail<SHIFT_LANES>(s_tree, tid);
+    if (tid == 0)
+        upd_publish(ctrl, changed, shift, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, it, max_iter,
+                    budget, tol);
 }
+
 
 // C := Cn (the centres k_upd published) and the next iteration's candidate
 // lists: a rebuild at Cn with the published budget (the new reference buffer
@@ -2935,26 +2775,25 @@ __global__ __launch_bounds__(TPB) void k_lists(Grid g, const float4 *__restrict_
 }
 
 // Centre update and candidate lists in ONE launch (D <= 3, K <= CAND_TPB * 2 =
-// 1024: configs 1-4).  Every block loads all K statistics rows (both parity
-// halves of `partials`, or the all-reduced buffer), the previous rows, the old
-// centres and both reference buffers together with the control words -- one
-// memory latency -- and computes all K new centres into LDS plus the
+// 1024: configs 1-4).  Every block loads all K statistics rows, the previous
+// rows, the old centres and both reference buffers together with the control
+// words -- one memory latency -- and computes all K new centres into LDS plus the
 // order-independent decisions every block needs identically (an empty cluster
 // halts; the largest drift and shift give rebuild-or-refresh and the new
 // budget).  Then one agent-scope arrival per block; the LAST block to arrive
 // (every other block's loads have returned by then) publishes what k_upd does
-// -- prev, held, the zeroed next accumulation target, C and the new reference
+// -- prev, held, the zeroed statistics, C and the new reference
 // buffer, the shift tree of oracle/lloyd_ref.py shift_total, history and flags
 // -- and every block rebuilds or refreshes its own cells' lists from the LDS
 // centres.  Replaces k_upd1 + k_lists (two launches, ~16 us at an 8-way slab).
-// PUB (round 6; the host takes it when one more block fits the residency, e.g.
+// PUB (the host takes it when one more block fits the residency, e.g.
 // the 8-way slab's 256 list blocks): the LAST block of the grid builds no lists
 // and is the publisher -- it waits (bounded, s_sleep) until the list blocks have
 // arrived, right after their centres, and publishes while they still build
 // their lists, instead of after its own lists; a wait past 2 s sets done = 5.
 template <int D, int R, bool PUB = false>
 __global__ __launch_bounds__(CAND_TPB) void k_updlists(
-    unsigned long long *__restrict__ stats_in, unsigned long long *__restrict__ partials, int K, QExp qe,
+    unsigned long long *__restrict__ stats, int K, QExp qe,
     unsigned long long *__restrict__ held, unsigned long long *__restrict__ prev, float4 *__restrict__ C,
     float4 *__restrict__ cref, unsigned long long *__restrict__ hist_changed, double *__restrict__ hist_shift,
     Ctrl *__restrict__ ctrl, double alpha, double dl_cap, Grid g, uint32_t *__restrict__ fc_cnt,
@@ -2963,42 +2802,21 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
     extern __shared__ __attribute__((aligned(16))) float4 cstage[];   // the K new centres
     DBG_T(13);
     unsigned gate = ctrl->halt | ctrl->done;
-    const uint32_t it = ctrl->iter, max_iter = ctrl->max_iter;
-    const unsigned sel = ctrl->ref_sel;
-    const double budget = ctrl->budget, tol = ctrl->tol;
+    uint32_t it = ctrl->iter, max_iter = ctrl->max_iter;
+    unsigned sel = ctrl->ref_sel;
+    double budget = ctrl->budget, tol = ctrl->tol;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = K * (D + 1);
     // row r of this thread: centroid j = tid + CAND_TPB * r (tree lane j).  (The
     // publisher alone loading the previous rows, for the changed-word count,
     // measured slower: its extra latency sits on the launch's tail.)
-    unsigned long long row[R][D + 1], alt[R][D + 1], pv[R][D + 1];
+    unsigned long long row[R][D + 1], pv[R][D + 1];
     float4 rj[R], rk[R], oj[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int j = tid + CAND_TPB * r;
-        if (j < K) {
-            const size_t o = (size_t)j * (D + 1);
-#pragma unroll
-            for (int a = 0; a <= D; ++a) {
-                row[r][a] = stats_in ? stats_in[o + a] : partials[o + a];
-                alt[r][a] = stats_in ? 0ull : partials[(size_t)n + o + a];
-                pv[r][a] = prev[o + a];
-            }
-            rj[r] = cref[j];
-            rk[r] = cref[(size_t)K + j];
-            oj[r] = C[j];
-        }
-    }
+    upd_load_rows<D, R, CAND_TPB>(tid, K, stats, prev, cref, C, row, pv, rj, rk, oj);
+    // keep the control-word loads above the exit, in flight with the rows
+    asm volatile("" : "+s"(gate), "+s"(it), "+s"(max_iter), "+s"(sel), "+s"(budget), "+s"(tol));
     if (gate != 0u) return;
     DBG_T(0);
-    const unsigned par = it & 1u;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        if (!stats_in && par)
-#pragma unroll
-            for (int a = 0; a <= D; ++a) row[r][a] = alt[r][a];
-        if (sel) rj[r] = rk[r];
-    }
     unsigned long long neq = 0ull;
     unsigned ne = 0u;
     double dr = 0.0, ds = 0.0, sh[R];
@@ -3009,23 +2827,14 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
         if (j < K) {
             double drj = 0.0, dsj = 0.0;
             float4 cnew;
-            upd_row<D>(row[r], pv[r], rj[r], oj[r], qe, cnew, neq, ne, drj, dsj);
+            upd_row<D>(row[r], pv[r], sel ? rk[r] : rj[r], oj[r], qe, cnew, neq, ne, drj, dsj);
             dr = fmax(dr, drj);
             ds = fmax(ds, dsj);
             sh[r] = dsj;
             cstage[j] = cnew;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        neq += __shfl_xor(neq, o);
-        ne += __shfl_xor(ne, o);
-        dr = fmax(dr, __shfl_xor(dr, o));
-        ds = fmax(ds, __shfl_xor(ds, o));
-    }
-    constexpr int NW = CAND_TPB / 64;
-    __shared__ unsigned long long s_neq[NW];
-    __shared__ unsigned s_ne[NW];
-    __shared__ double s_dr[NW], s_ds[NW];
+    __shared__ UpdSums<CAND_TPB / 64> sums;
     __shared__ unsigned s_last;
     // the shift tree's lanes: L < 1024 holds sh[L] (K <= 1024); the first halving
     // step (lane t += lane t + 512) runs in this thread's registers.  Kept in LDS
@@ -3034,7 +2843,7 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
     static_assert(CAND_TPB == SHIFT_LANES / 2, "thread t holds tree lanes t and t + 512");
     __shared__ double s_tree[CAND_TPB];
     s_tree[tid] = sh[0] + (R > 1 ? sh[R > 1 ? 1 : 0] : 0.0);
-    if (lane == 0) { s_neq[wv] = neq; s_ne[wv] = ne; s_dr[wv] = dr; s_ds[wv] = ds; }
+    upd_wave_sums(sums, tid, neq, ne, dr, ds);
     __syncthreads();   // every load of this block has returned (its values are used above)
     // The arrival: issued now, its returned place read after this block's lists.
     // One same-address atomic per block (512 of them serialise at the memory
@@ -3053,22 +2862,13 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
     } else {
         tk = arrive_issue(&ctrl->u_arrive, (unsigned long long)__builtin_amdgcn_readfirstlane(wv == 0 ? 1 : 0));
     }
-    // the decisions of upd_publish, identical in every block (same data, order-free maxima)
-    auto decide = [&](unsigned long long &n_empty, double &dmax, double &smax, bool &rebuild, double &dl_new) {
-        n_empty = 0ull; dmax = 0.0; smax = 0.0;
-        for (int w = 0; w < NW; ++w) {
-            n_empty += s_ne[w]; dmax = fmax(dmax, s_dr[w]); smax = fmax(smax, s_ds[w]);
-        }
-        const double slack = 1.0 + 9.094947017729282e-13;
-        rebuild = !(sqrt(dmax) * slack <= budget);
-        dl_new = alpha * sqrt(smax) * slack;
-        if (!(dl_new <= dl_cap)) dl_new = 0.0;
-    };
     {
-        unsigned long long n_empty;
+        // the decisions of upd_publish, identical in every block (same data, order-free maxima)
+        unsigned long long changed, n_empty;
         double dmax, smax, dl_new;
         bool rebuild;
-        decide(n_empty, dmax, smax, rebuild, dl_new);
+        upd_block_sums(sums, changed, n_empty, dmax, smax);
+        upd_decide(dmax, smax, budget, alpha, dl_cap, rebuild, dl_new);
         // this block's share of the writes nobody reads in this launch: the
         // relocation snapshot `held` and, on a rebuild, the new reference buffer
         // (the blocks read cref[sel ^ 1] only speculatively, and use cref[sel])
@@ -3118,27 +2918,21 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
     }
     DBG_T(3);
     // ---- the publisher: every other block's loads have returned.  It reads the
-    // rows again (L2; nobody has written them): prev := rows, the next
-    // accumulation target := 0 and (unless halted: the relocation needs the old
-    // C) C := the new centres.  Invariant the zeroing relies on: every
-    // block consumed its loads of prev, C and the statistics rows (their values
-    // feed the centres above) before it arrived; a load left in flight at an
-    // arrival is one whose value is discarded -- the `alt` half of `partials`,
-    // issued only when stats_in is null, a path no engine entry takes since
-    // round 6 (pcm_iterate / pcm_iter_global always pass the statistics buffer).
-    unsigned long long n_empty;
-    double dmax, smax, dl_new;
-    bool rebuild;
-    decide(n_empty, dmax, smax, rebuild, dl_new);
-    const unsigned long long *src = stats_in ? stats_in : partials + (size_t)par * n;
-    unsigned long long *pnext = stats_in ? stats_in : partials + (size_t)(par ^ 1u) * n;
+    // rows again (L2; nobody has written them): prev := rows, the statistics := 0
+    // for the next accumulation and (unless halted: the relocation needs the old
+    // C) C := the new centres.  Invariant the zeroing relies on: every block
+    // consumed its loads of prev, C and the statistics rows (their values feed
+    // the centres above) before it arrived.
+    unsigned long long changed, n_empty;
+    double dmax, smax;
+    upd_block_sums(sums, changed, n_empty, dmax, smax);
     unsigned long long v[R][D + 1];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int j = tid + CAND_TPB * r;
         const size_t o = (size_t)(j < K ? j : 0) * (D + 1);
 #pragma unroll
-        for (int a = 0; a <= D; ++a) v[r][a] = src[o + a];
+        for (int a = 0; a <= D; ++a) v[r][a] = stats[o + a];
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -3148,38 +2942,134 @@ __global__ __launch_bounds__(CAND_TPB) void k_updlists(
 #pragma unroll
             for (int a = 0; a <= D; ++a) prev[o + a] = v[r][a];
 #pragma unroll
-            for (int a = 0; a <= D; ++a) pnext[o + a] = 0ull;   // the next accumulation starts from zero
+            for (int a = 0; a <= D; ++a) stats[o + a] = 0ull;   // the next accumulation starts from zero
             if (n_empty == 0ull) C[j] = cstage[j];
         }
     }
-    unsigned long long changed = 0ull;
-    for (int w = 0; w < NW; ++w) changed += s_neq[w];
+    // (read again after the stores: the totals stay out of registers through them)
+    upd_block_sums(sums, changed, n_empty, dmax, smax);
     if (tid == 0) {
         held[n] = 0ull;
-        if (stats_in) stats_in[n] = 0ull;
+        stats[n] = 0ull;
         __hip_atomic_store(&ctrl->u_arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (n_empty > 0ull) {
-        if (tid == 0) {
-            ctrl->n_empty = (unsigned)n_empty;
-            ctrl->neq_saved = changed;
-            ctrl->lists = 0u;
-            ctrl->halt = 1u;
-        }
+        if (tid == 0) upd_halt(ctrl, n_empty, changed);
     } else {
-        for (int h = SHIFT_LANES / 4; h >= 64; h >>= 1) {
-            if (tid < h) s_tree[tid] = s_tree[tid] + s_tree[tid + h];
-            __syncthreads();
-        }
-        if (wv == 0) {
-            double x = s_tree[lane];
-            for (int st = 32; st > 0; st >>= 1) x = x + __shfl_down(x, st);   // lane t: x_t + x_{t+st}
-            if (lane == 0)
-                upd_publish(ctrl, changed, x, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, it,
-                            max_iter, budget, tol);
-        }
+        const double shift = shift_tree_tail<CAND_TPB>(s_tree, tid);
+        if (tid == 0)
+            upd_publish(ctrl, changed, shift, dmax, smax, sel, alpha, dl_cap, hist_changed, hist_shift, it, max_iter,
+                        budget, tol);
     }
     DBG_T(6);
+}
+
+// The update of an iteration that halted on an empty cluster, after the host's
+// relocation (k_reloc_apply gave the empty clusters their points in `held`,
+// which the host copied to `stats`, and set ctrl->resume).  One block of
+// SHIFT_LANES threads: averages (a cluster still empty takes the largest
+// cluster's new centre, lowest index on ties), the shift with the tree of
+// oracle/lloyd_ref.py shift_total (thread L sums j = L + 1024 r in ascending
+// r), zeroes `stats` and publishes history and flags with the changed-word
+// count the halted update saved.  It leaves ctrl->lists and the drift budget
+// alone: the k_cand that follows rebuilds the lists at the new C.
+template <int D>
+__global__ __launch_bounds__(SHIFT_LANES) void k_resume(unsigned long long *__restrict__ stats, int K, QExp qe,
+                                                        float4 *__restrict__ C, float4 *__restrict__ Cn,
+                                                        unsigned long long *__restrict__ hist_changed,
+                                                        double *__restrict__ hist_shift, Ctrl *__restrict__ ctrl) {
+    if (gated(ctrl)) return;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = K * (D + 1);
+    constexpr int NW = SHIFT_LANES / 64;
+    __shared__ unsigned cnt_empty;
+    __shared__ unsigned long long wmax[NW];
+    __shared__ int warg[NW];
+    __shared__ double ssum[SHIFT_LANES];
+    if (tid == 0) cnt_empty = 0;
+    __syncthreads();
+    unsigned long long bmax = 0;
+    int barg = 0x7fffffff;
+    unsigned ne = 0;
+    for (int j = tid; j < K; j += SHIFT_LANES) {
+        const unsigned long long c = stats[(size_t)j * (D + 1) + D];
+        if (c == 0) ne++;
+        if (c > bmax) { bmax = c; barg = j; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long ob = __shfl_xor(bmax, o);
+        const int oa = __shfl_xor(barg, o);
+        if (ob > bmax || (ob == bmax && oa < barg)) { bmax = ob; barg = oa; }
+    }
+    if (lane == 0) { wmax[wv] = bmax; warg[wv] = barg; }
+    if (ne) atomicAdd(&cnt_empty, ne);
+    __syncthreads();
+    unsigned long long gmax = wmax[0];
+    int argmax = warg[0];
+    for (int w = 1; w < NW; ++w)
+        if (wmax[w] > gmax || (wmax[w] == gmax && warg[w] < argmax)) { gmax = wmax[w]; argmax = warg[w]; }
+    auto mean_of = [&](int j, float4 &cn) -> bool {
+        unsigned long long row[D + 1];
+#pragma unroll
+        for (int a = 0; a <= D; ++a) row[a] = stats[(size_t)j * (D + 1) + a];
+        cn = row_mean<D>(row, qe);
+        return row[D] > 0;
+    };
+    auto shift_of = [&](const float4 &a4, const float4 &b4) -> double {
+        double sh = 0.0;
+#pragma unroll
+        for (int a = 0; a < D; ++a) {
+            const double dd = (double)comp(a4, a) - (double)comp(b4, a);
+            const double sq = dd * dd;
+            sh = (a == 0) ? sq : sh + sq;
+        }
+        return sh;
+    };
+    double acc = 0.0;   // tree lane tid: the shifts of j = tid + 1024 r in ascending r
+    if (cnt_empty == 0) {   // the common case: no empty cluster, one pass
+        for (int j = tid; j < K; j += SHIFT_LANES) {
+            const float4 b4 = C[j];
+            float4 cn;
+            mean_of(j, cn);
+            acc = acc + shift_of(cn, b4);
+            C[j] = cn;
+        }
+    } else {   // an empty cluster copies the largest one's centre
+        for (int j = tid; j < K; j += SHIFT_LANES) {
+            float4 cn;
+            if (mean_of(j, cn)) Cn[j] = cn;
+        }
+        __syncthreads();   // Cn[argmax] is read by other threads
+        for (int j = tid; j < K; j += SHIFT_LANES) {
+            const unsigned long long c = stats[(size_t)j * (D + 1) + D];
+            if (c == 0) Cn[j] = (gmax > 0) ? Cn[argmax] : C[j];
+            const float4 a4 = Cn[j], b4 = C[j];
+            acc = acc + shift_of(a4, b4);
+            C[j] = Cn[j];
+        }
+    }
+    ssum[tid] = acc;
+    __syncthreads();
+    // zero the statistics for the next iteration's accumulation (every read above precedes the barrier)
+    for (int i = tid; i < n + 1; i += SHIFT_LANES) stats[i] = 0ull;
+    const double shift = shift_tree_tail<SHIFT_LANES>(ssum, tid);
+    if (tid == 0) {
+        const unsigned long long changed = ctrl->neq_saved;
+        const uint32_t it = ctrl->iter;
+        if (it < ctrl->max_iter) {
+            hist_changed[it] = changed;
+            hist_shift[it] = shift;
+        }
+        ctrl->last_changed = changed;
+        ctrl->last_shift = shift;
+        ctrl->resume = 0u;
+        uint32_t done = 0;
+        if (changed == 0ull) done = 1u;
+        else if (shift <= ctrl->tol) done = 2u;
+        ctrl->iter = it + 1;
+        if (!done && it + 1 >= ctrl->max_iter) done = 3u;
+        ctrl->done = done;
+    }
 }
 
 // ------------------------------------------------------------------ relocation

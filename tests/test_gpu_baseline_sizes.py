@@ -9,8 +9,8 @@ GPU box's host cores), on the same points:
   device-generated cloud is copied to the host so both sides see identical
   bits) -- exercises the >2^26-point, multi-GB buffer addressing of k_lloyd;
 * config 5 shard: N=62.5M (one of eight ranks' rows), K=4096, D=4 fp16,
-  2 iterations -- the K > 2048 non-fused update path (k_global + k_cand) and
-  long candidate lists.
+  2 iterations -- the K > 2048 non-fused update path (k_upd + k_coarse +
+  k_lists) and long candidate lists.
 
 Bar: labels bit-exact, centres bitwise equal, same n_iter, per-iteration
 change records zero together, inertia bitwise equal (exact integer sum).

@@ -348,6 +348,14 @@ def test_update_paths(pcm, fused, monkeypatch):
     C0[100:150] = C0[0]
     ref = R.lloyd_fit(Xr, C0, max_iter=15, fast=True)
     assert_same(gpu_fit(pcm, Xr, C0, 15), ref, f"fused={fused} relocation")
+    # 1024 < K <= 2048 (two rows per k_upd1 thread, k_lists staging the centres
+    # in LDS; too many centres for k_updlists under either setting) through a
+    # relocation and k_resume
+    Xm = R.splitmix_uniform(60_000, 3, 51)
+    C0 = Xm[R.init_indices(60_000, 1500)].copy()
+    C0[10:30] = C0[3]
+    ref = R.lloyd_fit(Xm, C0, max_iter=5, fast=True)
+    assert_same(gpu_fit(pcm, Xm, C0, 5), ref, f"fused={fused} k=1500 relocation")
 
 
 def test_update_paths_d4(pcm):
