@@ -29,7 +29,10 @@ in scikit-learn), with the canonical arithmetic of ``csrc/pcm_dense.hip``:
 
 Pinned against scikit-learn golden runs (``tests/golden/make_golden.py``,
 ``jasraj_*.npz``): labels and ``n_iter`` equal, centres within 1e-12
-(float64), inertia within 1e-12.
+(float64), inertia within 1e-12.  The relocation branches (empty clusters, an
+emptied donor, rows all on their centres) are pinned against
+``_kmeans_single_lloyd`` itself in ``tests/test_dense.py`` (float64 and float32:
+centres within 1e-12 / 1e-5).
 """
 from __future__ import annotations
 
@@ -76,7 +79,7 @@ def sqdist(X, C) -> np.ndarray:
 def assign(X, C):
     out = np.empty(X.shape[0], dtype=np.int32)
     dist = np.empty(X.shape[0], dtype=X.dtype)
-    step = max(1, 1 << 20 // max(1, C.shape[0] * X.shape[1]))
+    step = max(1, (1 << 20) // max(1, C.shape[0] * X.shape[1]))
     for s in range(0, X.shape[0], step):
         dd = sqdist(X[s:s + step], C)
         out[s:s + step] = np.argmin(dd, axis=1)
@@ -122,7 +125,8 @@ def inertia_exact(d, s: int) -> float:
 
 def dense_fit(X, C0, max_iter: int = 300, tol: float = 0.0):
     """``_kmeans_single_lloyd`` restated for the dense path; returns dict(labels,
-    centers, inertia, n_iter, strict, changed, shift)."""
+    centers, inertia, n_iter, strict, changed, shift, relocations); ``relocations``
+    counts the iterations in which at least one row moved into an empty cluster."""
     X = points(X)
     T = X.dtype
     C = np.ascontiguousarray(np.asarray(C0, dtype=T))
@@ -136,6 +140,7 @@ def dense_fit(X, C0, max_iter: int = 300, tol: float = 0.0):
     strict = False
     changed, shifts = [], []
     it = 0
+    relocations = 0
     for it in range(max_iter):
         labels, dist = assign(X, C)
         nch = int(np.count_nonzero(labels != labels_old))
@@ -146,6 +151,7 @@ def dense_fit(X, C0, max_iter: int = 300, tol: float = 0.0):
         if empty.size:
             order = np.lexsort((np.arange(n), -dist.astype(np.float64)))
             if float(dist[order[0]]) > 0.0:
+                relocations += 1
                 for t, j in enumerate(empty[:n]):
                     p = order[t]
                     old = labels[p]
@@ -172,4 +178,4 @@ def dense_fit(X, C0, max_iter: int = 300, tol: float = 0.0):
         labels_old = labels
     labels, dist = assign(X, C)
     return dict(labels=labels, centers=C, inertia=inertia_exact(dist, inertia_scale(maxabs)), n_iter=it + 1,
-                strict=strict, changed=changed, shift=shifts)
+                strict=strict, changed=changed, shift=shifts, relocations=relocations)

@@ -87,6 +87,106 @@ def test_estimator_random_state_none_uses_global_stream():
     np.testing.assert_array_equal(out[0], out[1])
 
 
+# ---------------------------------------------------------------- oracle: chunking, relocation pins
+def test_dense_oracle_assign_chunks_equal_rows():
+    """DR.assign walks the rows in chunks of (1 << 20) // (k * d): here 1365 rows,
+    neither 1 nor >= n, and n = 3 * 1365 + 905 leaves a ragged last chunk.  Labels and
+    distances equal a row-by-row evaluation bit for bit, in both dtypes."""
+    n, d, k = 5000, 12, 64
+    step = (1 << 20) // (k * d)
+    assert 1 < step < n and n % step != 0
+    rng = np.random.default_rng(11)
+    for dt in (np.float32, np.float64):
+        X = rng.normal(0, 2, (n, d)).astype(dt)
+        C = X[rng.integers(0, n, k)].copy()
+        C[5] = C[3]                                                   # an exact tie: the lower index wins
+        labels, dist = DR.assign(X, C)
+        assert labels.dtype == np.int32 and dist.dtype == dt
+        want_l = np.empty(n, np.int32)
+        want_d = np.empty(n, dt)
+        for i in range(n):
+            dd = DR.sqdist(X[i:i + 1], C)[0]
+            want_l[i] = np.argmin(dd)
+            want_d[i] = dd[want_l[i]]
+        np.testing.assert_array_equal(labels, want_l)
+        np.testing.assert_array_equal(dist, want_d)
+        assert not np.any(labels == 5)
+
+
+def reloc_case(name, dtype=np.float64):
+    """The relocation inputs shared by the scikit-learn pins below and by
+    tests/test_gpu_dense_edges.py: (X, C0, max_iter)."""
+    if name == "a":         # three empty clusters (the test_gpu_dense_relocation input)
+        X = np.random.default_rng(5).normal(0, 1, (2000, 12))
+        C0 = np.concatenate([X[:4], np.full((3, 12), 40.0) + np.arange(3)[:, None]])
+        it = 40
+    elif name in ("b1", "b2"):
+        # donor emptied: row 3 is alone in cluster 2 and the farthest from its centre, so it
+        # moves into the empty cluster 0 and leaves cluster 2 with no row (count 0, not in
+        # the list of empty clusters fixed before the moves): cluster 2 copies the largest.
+        # max_iter >= 3 is left out on purpose: scikit-learn's float sums leave a centre one
+        # ulp off 0.05 and it runs one more iteration; the exact sums here stop.
+        X = np.zeros((4, 2))
+        X[:, 0] = [0.0, 0.1, 0.2, 100.0]
+        C0 = np.zeros((3, 2))
+        C0[:, 0] = [1000.0, 0.0, 90.0]
+        it = int(name[1])
+    elif name == "c":
+        # 300 + 200 identical far rows scattered over the cloud, 12 empty clusters: the 12
+        # farthest rows tie exactly (row order decides) and are one point, so 11 clusters
+        # are empty again in the next iteration and take rows of the second group
+        rng = np.random.default_rng(17)
+        X = rng.normal(0, 1, (3000, 6))
+        far = rng.permutation(3000)[:500]
+        X[far[:300]] = np.array([30.0, -30.0, 30.0, -30.0, 30.0, -30.0])
+        X[far[300:]] = np.array([-20.0, 20.0, -20.0, 20.0, -20.0, 20.0])
+        keep = np.setdiff1d(np.arange(3000), far)[:4]
+        C0 = np.concatenate([X[keep], np.full((12, 6), 500.0) + np.arange(12)[:, None]])
+        it = 12
+    elif name == "d":
+        # every row on its centre and two empty clusters: nothing moves (the early return of
+        # _relocate_empty_clusters_dense), the empty clusters copy the first largest one.
+        # The empty clusters come after it: scikit-learn copies an already averaged centre
+        # only then (_average_centers runs in cluster order).
+        rows = np.array([[1.0, 2.0, 3.0], [-4.0, 0.5, 7.0], [9.0, -1.0, 0.25]])
+        X = np.repeat(rows, 50, axis=0)[np.random.default_rng(3).permutation(150)]
+        C0 = np.concatenate([rows, [[70.0, 70.0, 70.0], [80.0, 80.0, 80.0]]])
+        it = 10
+    else:
+        raise KeyError(name)
+    return np.ascontiguousarray(X.astype(dtype)), np.ascontiguousarray(C0.astype(dtype)), it
+
+
+RELOC = [(c, dt) for c in ("a", "b1", "b2", "c", "d") for dt in (np.float64, np.float32)]
+RELOC_IDS = [f"{c}-{np.dtype(dt).name}" for c, dt in RELOC]
+# iterations in which at least one row moves, as the construction of each case fixes it
+# (a: the first; b: every one; d: none; c: the first three: 12 rows of the first group
+# move, then all 300 of them choose the first of their 12 equal centres and 11 rows of the
+# second group move, then those 200 choose the first of their 11 and 10 distinct rows move)
+RELOC_COUNT = {"a": 1, "b1": 1, "b2": 2, "c": 3, "d": 0}
+
+
+@pytest.mark.parametrize("case,dtype", RELOC, ids=RELOC_IDS)
+def test_dense_oracle_relocation_matches_sklearn(case, dtype):
+    """DR.dense_fit against scikit-learn's internal single run (KMeans itself would centre
+    X) where clusters run empty: labels and n_iter equal, centres within the bars of
+    oracle/dense_ref.py's docstring."""
+    pytest.importorskip("sklearn")
+    from sklearn.cluster._kmeans import _kmeans_single_lloyd
+    X, C0, max_iter = reloc_case(case, dtype)
+    r = DR.dense_fit(X, C0, max_iter=max_iter, tol=0.0)
+    labels, inertia, centers, n_iter = _kmeans_single_lloyd(X, np.ones(len(X), dtype), C0.copy(), max_iter,
+                                                            verbose=False, tol=0.0, n_threads=1)
+    assert centers.dtype == dtype and r["centers"].dtype == dtype
+    np.testing.assert_array_equal(r["labels"], labels)
+    assert r["n_iter"] == n_iter
+    bar = 1e-12 if dtype == np.float64 else 1e-5
+    np.testing.assert_allclose(r["centers"], centers, rtol=bar, atol=bar)
+    assert r["relocations"] == RELOC_COUNT[case]
+    if case == "d":
+        np.testing.assert_array_equal(r["centers"][3:], r["centers"][[0, 0]])
+
+
 # ---------------------------------------------------------------- GPU
 @pytest.fixture(scope="module")
 def gpu():
@@ -143,7 +243,7 @@ def test_gpu_dense_relocation(gpu):
     ref = DR.dense_fit(X, C0, max_iter=40)
     res = dense_fit(torch.from_numpy(X).cuda(), torch.from_numpy(C0).cuda(), max_iter=40)
     torch.cuda.synchronize()
-    assert res.relocations >= 1
+    assert res.relocations == ref["relocations"] == 1
     np.testing.assert_array_equal(res.labels.cpu().numpy(), ref["labels"])
     np.testing.assert_array_equal(res.centers.cpu().numpy(), ref["centers"])
     assert res.n_iter == ref["n_iter"]
