@@ -79,6 +79,7 @@ struct pcm_engine {
     uint32_t *torig = nullptr;       // ... and its inverse
     size_t cap_tsum = 0, cap_tpos = 0, cap_torig = 0;
     bool sole_on = true;             // PCM_SOLE=0 (A/B, read by pcm_fit_begin): every owner word stays 0
+    bool fast_on = true;             // PCM_FAST=0 (A/B and tests, read by pcm_fit_begin): every tile takes k_lloyd1's generic body
     // crowded layouts (tight clusters): Morton levels of the in-cell order and the tile lists
     int zlev = 0;
     float4 *tbox = nullptr;          // [tile][2] exact point box
@@ -914,6 +915,8 @@ int pcm_fit_begin(pcm_engine *e, const float *C0, double tol, int max_iter, void
     {   // read per fit, so tests and A/B runs can switch it between fits of one process
         const char *v = std::getenv("PCM_SOLE");
         e->sole_on = !(v && std::atoi(v) == 0);
+        const char *f = std::getenv("PCM_FAST");
+        e->fast_on = !(f && std::atoi(f) == 0);
     }
     e->fit_ready = true;
     // candidate lists of C0 (later iterations get theirs from k_lists / the resume path)
@@ -1048,6 +1051,7 @@ static int assign_ls(const pcm_engine *e) {
 static LloydArgs lloyd_args(pcm_engine *e) {
     LloydArgs A{};
     A.xcd = ((xcd_mode() >> 1) & 1) && !e->tiles_lpt;   // an ordered tile list is dealt round-robin
+    A.fast = e->fast_on ? 1 : 0;
     A.xs = e->xs;
     A.xz = e->use_xz ? e->xz : nullptr;
     A.tmeta = e->use_xz ? e->tmeta : nullptr;

@@ -1571,6 +1571,7 @@ struct LloydArgs {
     const float4 *tbox;             // crowded layouts: [tile][2] exact point box (lo, hi), else null
     const int32_t *tl_lab;
     int xcd;                        // k_lloyd1 takes its tile through xcd_block
+    int fast;                       // short-list tiles take k_lloyd1's lean rounds (PCM_FAST=0: none does)
 };
 
 struct TileL {
@@ -1749,7 +1750,12 @@ __global__ __launch_bounds__(TPB) void k_label(LloydArgs A, void *lab, unsigned 
 // _k_means_lloyd.pyx:205-213) in LDS; a winner's fixed-point coordinates and
 // count are summed into LDS words of its lane slot (ds_add_u32, lane-minor:
 // conflict-free), winners without a slot into int64 words; out-of-tile lanes of
-// a partial round add into a junk slot (never read).
+// a partial round add into a junk slot (never read).  A tile whose list fits
+// the lane slots -- nearly every tile of a fine grid -- takes lean rounds (see
+// `lean` below): no slot map, no overflow test, and in the rounds that lie
+// wholly inside the tile no in-tile test either (config 3: 72.1M -> 67.1M VALU
+// and 32.8M -> 25.4M SALU wave-instructions per launch, k_lloyd1 164 -> 155 us,
+// profiles/fastpath_ab.txt).
 // Nearest of mm centres read through scalar loads (FULL tiles: the whole
 // uniform centre array); same scan order and tie rule as scan4.
 template <int D>
@@ -1907,6 +1913,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
         l0 = fc_lab[(size_t)cell * CAPF + tid];
     }
     uint32_t cnt = fc_cnt[cell];
+    // Lean rounds (below) exist in the 8-slot instances that keep their parent's
+    // waves per SIMD with them: not fp16 D = 3 and 4 (64 -> 69 and 72 VGPRs,
+    // 8 -> 7 waves) nor the D = 4 16-slot instance (fp32 80 -> 101 VGPRs, 6 -> 4).
+    constexpr bool kFast = !MASK && !CROWD && LS < LSLOT && !(sizeof(T) == 2 && D >= 3);
     DBG_LV(7, (unsigned long long)(cnt & 0xFFFFu) | ((unsigned long long)(end - start) << 16));
     // crowded cell (list FULL or past TL_MIN): the tile's own list when k_tile_cand built a shorter one
     // (lists past TLCAP and all-K scans go through LDS in chunks, below)
@@ -2108,6 +2118,9 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
 #pragma unroll
             for (int a = 0; a < D; ++a) ctr[a] = (float)(A.g.lo[a] + ((double)ci[a] + 0.5) * A.g.w[a]);
         }
+        // (kept rolled: interleaved eight-fold this rare loop held 24 VGPRs, the peak of the fp32 D = 3
+        // instance: 71 -> 69)
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
         for (int j = tid; j < mm; j += TPB) skey[j] = dist_canon<D>(ctr, crec[j]);
         __syncthreads();
         for (int j = tid; j < mm; j += TPB) {
@@ -2201,6 +2214,13 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     constexpr int NL = ZC ? 2 : Raw<T, D>::NW / 4 + (Raw<T, D>::NW % 4 ? 1 : 0);
     constexpr int VM = PF * NL;
     constexpr int WAIT_PREV = 0x0F70 | (VM & 0xF) | ((VM >> 4) << 14);   // vmcnt(VM) expcnt(7) lgkmcnt(15)
+    // lean: a list no longer than the lane slots (never an all-K scan; never
+    // MASK or CROWD, so no masks, tile lists or chunks): list position = lane
+    // slot, so a round skips everything that exists for winners without a
+    // slot -- the slot map, the `sm >= LS` test, the `over` reduction, the
+    // int64 words.  Block-uniform, decided once per block; the generic code
+    // serves every other tile, and every tile when PCM_FAST=0.
+    const bool lean = kFast && A.fast && !can_over;
     auto step = [&](Raw<T, D> &cx, Raw<T, D> &nx, int r) {
         ldx(nx, item_off(r + PF));
         if (r >= nr) {
@@ -2237,6 +2257,30 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
             } else {
                 scan4<D>(crec, mm, x, bd, bj);
             }
+        }
+        if (kFast && lean) {
+            // list position = lane slot.  A round that lies wholly inside the
+            // tile (block-uniform; all but a tile's first and last) takes the
+            // slot address straight from the winner; the others send their
+            // out-of-tile points to the junk slot.  Neither arm issues or waits
+            // for a point load, so both reach the loop latch with the same
+            // outstanding loads (see the padding step above).
+            auto add4 = [&](const int (&sl)[4]) {
+                for (int e = 0; e < 4; ++e) {
+                    uint32_t *ap = myacc + sl[e] * ((D + 1) * AW);
+                    for (int a = 0; a < D; ++a) atomicAdd(ap + a * AW, (uint32_t)fixed_i(x[e][a], A.q[a]));
+                    atomicAdd(ap + D * AW, 1u);
+                }
+            };
+            const bool whole = (rbase >= start) && (rbase + 4u * TPB <= end);
+            if (whole) {
+                add4(bj);
+            } else {
+                int sl[4];
+                for (int e = 0; e < 4; ++e) sl[e] = ((i0 + e >= start) && (i0 + e < end)) ? bj[e] : LS;
+                add4(sl);
+            }
+            return;
         }
         // block-uniform: every point of the round lies inside the tile
         const bool whole = (rbase >= start) && (rbase + 4u * TPB <= end);
