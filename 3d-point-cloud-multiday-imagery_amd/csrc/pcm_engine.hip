@@ -80,6 +80,7 @@ struct pcm_engine {
     size_t cap_tsum = 0, cap_tpos = 0, cap_torig = 0;
     bool sole_on = true;             // PCM_SOLE=0 (A/B, read by pcm_fit_begin): every owner word stays 0
     bool fast_on = true;             // PCM_FAST=0 (A/B and tests, read by pcm_fit_begin): every tile takes k_lloyd1's generic body
+    bool tilecost_on = true;         // PCM_TILECOST=0 (A/B and tests, read by pcm_fit_begin): a wave computes every round of its tile, in range or not
     // crowded layouts (tight clusters): Morton levels of the in-cell order and the tile lists
     int zlev = 0;
     float4 *tbox = nullptr;          // [tile][2] exact point box
@@ -376,7 +377,7 @@ void make_grid(Grid &g, int d, const double *lo, const double *hi, double target
 }
 
 // The Lloyd engine's pruning grid: about min(32 K, n / 2800) cells -- ~2.8k
-// points per cell: fewer, fuller tiles (a tile round is 1024 points) outweigh
+// points per cell: fewer, fuller tiles (a tile round is 512 points) outweigh
 // the slightly longer candidate lists (swept on 12.5M / 100M clouds).
 void choose_grid(pcm_engine *e) {
     // D = 4: smaller cells (~1k points) shorten the lists more than the tiles
@@ -917,6 +918,8 @@ int pcm_fit_begin(pcm_engine *e, const float *C0, double tol, int max_iter, void
         e->sole_on = !(v && std::atoi(v) == 0);
         const char *f = std::getenv("PCM_FAST");
         e->fast_on = !(f && std::atoi(f) == 0);
+        const char *tc = std::getenv("PCM_TILECOST");
+        e->tilecost_on = !(tc && std::atoi(tc) == 0);
     }
     e->fit_ready = true;
     // candidate lists of C0 (later iterations get theirs from k_lists / the resume path)
@@ -1052,6 +1055,7 @@ static LloydArgs lloyd_args(pcm_engine *e) {
     LloydArgs A{};
     A.xcd = ((xcd_mode() >> 1) & 1) && !e->tiles_lpt;   // an ordered tile list is dealt round-robin
     A.fast = e->fast_on ? 1 : 0;
+    A.tilecost = e->tilecost_on ? 1 : 0;
     A.xs = e->xs;
     A.xz = e->use_xz ? e->xz : nullptr;
     A.tmeta = e->use_xz ? e->tmeta : nullptr;

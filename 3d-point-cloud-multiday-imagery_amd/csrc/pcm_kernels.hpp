@@ -1572,6 +1572,7 @@ struct LloydArgs {
     const int32_t *tl_lab;
     int xcd;                        // k_lloyd1 takes its tile through xcd_block
     int fast;                       // short-list tiles take k_lloyd1's lean rounds (PCM_FAST=0: none does)
+    int tilecost;                   // a wave with no point of the tile in a round skips it (PCM_TILECOST=0: it computes it)
 };
 
 struct TileL {
@@ -1755,7 +1756,11 @@ __global__ __launch_bounds__(TPB) void k_label(LloydArgs A, void *lab, unsigned 
 // `lean` below): no slot map, no overflow test, and in the rounds that lie
 // wholly inside the tile no in-tile test either (config 3: 72.1M -> 67.1M VALU
 // and 32.8M -> 25.4M SALU wave-instructions per launch, k_lloyd1 164 -> 155 us,
-// profiles/fastpath_ab.txt).
+// profiles/fastpath_ab.txt).  Outside the rounds a tile zeroes only the slot rows
+// its fold reads and folds them with 16-byte reads and DPP row sums
+// (PCM_ZERO_LIVE, PCM_FOLD_DPP below), and a wave computes only the rounds in
+// which it has a point of the tile (`nrw`; config 3: 66.6M -> 61.9M VALU and
+// 8.25M -> 6.40M LDS wave-instructions per launch, profiles/tilecost_ab.txt).
 // Nearest of mm centres read through scalar loads (FULL tiles: the whole
 // uniform centre array); same scan order and tie rule as scan4.
 template <int D>
@@ -1828,6 +1833,27 @@ constexpr int MASK_MIN = PCM_MASK_MIN;   // sub-cell masks for lists of at least
 #define PCM_ZPF 2
 #endif
 constexpr int ZPF = PCM_ZPF;
+// A tile's fixed cost outside its rounds.  PCM_ZERO_LIVE: only the slot rows
+// the fold reads are zeroed (min(list, slots) * (D + 1) rows of AW words, 16-byte
+// stores, once the list's length is in) -- never the junk slot, which is
+// written and never read.  PCM_FOLD_DPP: the fold reads each thread's four words
+// with one 16-byte load, sums their low and high 16-bit halves in int32 and
+// reduces both over the 16-lane DPP row (no ds_bpermute, no 64-bit shuffles).
+#ifndef PCM_ZERO_LIVE
+#define PCM_ZERO_LIVE 1
+#endif
+#ifndef PCM_FOLD_DPP
+#define PCM_FOLD_DPP 1
+#endif
+// sum of v over the lane's DPP row (16 lanes), valid in the row's last lane:
+// row_shr 8, 4, 2, 1, lanes shifted in from outside the row read 0
+__device__ __forceinline__ int row16_sum_last(int v) {
+    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);
+    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);
+    return v;
+}
 template <typename T, int D, int LS, bool MASK>
 constexpr int lloyd1_wpe() {
     return (sizeof(T) == 4 && D <= 3 && LS < LSLOT && !MASK) ? (ZPF > 2 ? 5 : PCM_WPE_FINE)
@@ -1971,7 +1997,10 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     Raw<T, D> xr[PF + 1];
 #pragma unroll
     for (int k = 0; k < PF; ++k) ldx(xr[k], item_off(k));
-    for (int e = tid; e < AccL<D, LS>::words; e += TPB) acc[e] = 0u;
+    // (not the crowded D = 1 instances: the later zeroing took them from 99 to 103 SGPRs, 8 -> 7 waves)
+    constexpr bool kZeroLive = PCM_ZERO_LIVE && !(CROWD && D == 1);
+    if constexpr (!kZeroLive)
+        for (int e = tid; e < AccL<D, LS>::words; e += TPB) acc[e] = 0u;
     // long tile lists: block-shared int64 words per list position (AccL::gwords, crowded launches only)
     unsigned long long *const govf =
         reinterpret_cast<unsigned long long *>(acc + (AccL<D, LS>::words + 1) / 2 * 2);
@@ -1985,6 +2014,14 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     // block-uniform: a winner can lack a lane slot only in an all-K scan or a
     // list longer than the slots (the per-round test below is skipped otherwise)
     const bool can_over = full || mm > LS;
+    if constexpr (kZeroLive) {
+        // the rows the fold reads: winners with a lane slot land in slots below
+        // min(mm, LS) on every path (short list: position; slot map: rank < LS;
+        // all-K scan: centroid < min(K, LS)); everything else goes to the junk slot
+        const int nz = (mm < LS ? mm : LS) * (D + 1) * (AW / 4);
+        uint4 *const a4 = reinterpret_cast<uint4 *>(acc);
+        for (int e = tid; e < nz; e += TPB) a4[e] = make_uint4(0u, 0u, 0u, 0u);
+    }
     if (kOvf && use_map)
         for (int e = tid; e < mm * (D + 1); e += TPB) ovf[e] = 0ull;
     if (full || chunked) {
@@ -2221,10 +2258,20 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     // int64 words.  Block-uniform, decided once per block; the generic code
     // serves every other tile, and every tile when PCM_FAST=0.
     const bool lean = kFast && A.fast && !can_over;
+    // The rounds in which this wave has a point of the tile (wave-uniform, in a
+    // scalar register).  A wave covers 256 of a round's points, and base0 <= start
+    // < base0 + 4, so its rounds are 0 .. nrw - 1: of a last round that holds a
+    // few dozen points the upper wave owns none, and a tile below 256 points
+    // gives it no round at all.  It takes the padding step there -- there is
+    // no barrier inside the round loop -- and its loop ends at nrw.
+    // PCM_TILECOST=0: nrw = nr, every wave computes every round.
+    const unsigned wfirst = base0 + (unsigned)__builtin_amdgcn_readfirstlane((tid >> 6) * (4 * 64));
+    const int nrw = !A.tilecost ? nr : (end > wfirst ? (int)((end - wfirst + 4 * TPB - 1) / (4 * TPB)) : 0);
     auto step = [&](Raw<T, D> &cx, Raw<T, D> &nx, int r) {
         ldx(nx, item_off(r + PF));
-        if (r >= nr) {
-            // padding step (nr not a multiple of 3): no compute, but the same
+        if (r >= nrw) {
+            // padding step (nr not a multiple of 3, or a round in which this
+            // wave has no point): no compute, but the same
             // wait as a computing step, so that every path reaches the loop
             // latch with the same outstanding loads (a skipped step left the
             // waitcnt pass a pessimistic merge: vmcnt(0) before each prefetch)
@@ -2325,7 +2372,7 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
         }
     };
     // PF+1 rotating register sets; a tile spans at most TILE / (4 TPB) + 1 = 9 rounds
-    for (int r = 0; r < nr; r += PF + 1) {
+    for (int r = 0; r < nrw; r += PF + 1) {
 #pragma unroll
         for (int k = 0; k <= PF; ++k) step(xr[k], xr[(k + PF) % (PF + 1)], r + k);
     }
@@ -2335,24 +2382,49 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(lloyd1_wpe_
     {
         const int nslots = mm < LS ? mm : LS;
         const int npairs = nslots * (D + 1);
-        for (int p0 = 0; p0 < npairs; p0 += TPB / 16) {
-            const int pi = p0 + tid / 16, sub = tid & 15;
-            long long sacc = 0;
-            if (pi < npairs) {
-                const bool isc = (pi % (D + 1) == D);
-                const uint32_t *row = acc + pi * AW;
-                for (int k = 0; k < AW / 16; ++k) {
-                    const uint32_t w = row[sub + 16 * k];
-                    sacc += isc ? (long long)w : (long long)(int32_t)w;
+        if constexpr (PCM_FOLD_DPP && AW == 64) {
+            // thread `sub` of a row takes words 4 sub .. 4 sub + 3 (any partition of
+            // the 64 words is the same integer sum).  w = (w >> 16) * 2^16 +
+            // (w & 0xffff) with an arithmetic shift; 64 low halves sum below 2^22
+            // and 64 high halves within +-2^21, so both int32 sums are exact, and
+            // the row's last lane rebuilds the int64 sum.  Count words are <= 64,
+            // so reading them as signed changes nothing.
+            for (int p0 = 0; p0 < npairs; p0 += TPB / 16) {
+                const int pi = p0 + tid / 16, sub = tid & 15;
+                int lo = 0, hi = 0;
+                if (pi < npairs) {
+                    const uint4 w = reinterpret_cast<const uint4 *>(acc + pi * AW)[sub];
+                    lo = (int)((w.x & 0xffffu) + (w.y & 0xffffu) + (w.z & 0xffffu) + (w.w & 0xffffu));
+                    hi = ((int32_t)w.x >> 16) + ((int32_t)w.y >> 16) + ((int32_t)w.z >> 16) + ((int32_t)w.w >> 16);
+                }
+                lo = row16_sum_last(lo);
+                hi = row16_sum_last(hi);
+                const long long sacc = (long long)hi * 65536 + (long long)lo;
+                if (pi < npairs && sub == 15 && sacc) {
+                    const int slot = pi / (D + 1), qq = pi % (D + 1);
+                    atomicAdd(prep + (size_t)sid[slot] * (D + 1) + qq, (unsigned long long)sacc);
                 }
             }
-            sacc += __shfl_down(sacc, 8, 16);
-            sacc += __shfl_down(sacc, 4, 16);
-            sacc += __shfl_down(sacc, 2, 16);
-            sacc += __shfl_down(sacc, 1, 16);
-            if (pi < npairs && sub == 0 && sacc) {
-                const int slot = pi / (D + 1), qq = pi % (D + 1);
-                atomicAdd(prep + (size_t)sid[slot] * (D + 1) + qq, (unsigned long long)sacc);
+        } else {
+            for (int p0 = 0; p0 < npairs; p0 += TPB / 16) {
+                const int pi = p0 + tid / 16, sub = tid & 15;
+                long long sacc = 0;
+                if (pi < npairs) {
+                    const bool isc = (pi % (D + 1) == D);
+                    const uint32_t *row = acc + pi * AW;
+                    for (int k = 0; k < AW / 16; ++k) {
+                        const uint32_t w = row[sub + 16 * k];
+                        sacc += isc ? (long long)w : (long long)(int32_t)w;
+                    }
+                }
+                sacc += __shfl_down(sacc, 8, 16);
+                sacc += __shfl_down(sacc, 4, 16);
+                sacc += __shfl_down(sacc, 2, 16);
+                sacc += __shfl_down(sacc, 1, 16);
+                if (pi < npairs && sub == 0 && sacc) {
+                    const int slot = pi / (D + 1), qq = pi % (D + 1);
+                    atomicAdd(prep + (size_t)sid[slot] * (D + 1) + qq, (unsigned long long)sacc);
+                }
             }
         }
         // the int64 words of the positions without a lane slot (use_map lists)
