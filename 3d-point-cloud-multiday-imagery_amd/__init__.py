@@ -19,6 +19,7 @@ kmeans_fuse(clouds, n_clusters, ...)                   -> napari layer tuples
 kmeans_assign(clouds, model)                           -> a later day's cloud labelled against a fused model
 cluster_stats(X, labels, n_clusters, groups=...)       -> ClusterStats: exact per-(day, cluster) counts, sums, second moments
 surface_elements(stats)                                -> per-cluster normal, roughness, planarity, rms (host, from the moments)
+height_grid(X, shape, cell_log2=, labels=, groups=...) -> HeightGrid: exact per-(day, pixel) count, height sum, top and bottom
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -29,7 +30,7 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "build_library", "kmeans_plusplus", "assemble_cloud", "KMeans", "dense_fit", "dense_kmeanspp",
            "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
-           "SurfaceElements"]
+           "SurfaceElements", "height_grid", "HeightGrid"]
 
 
 def __getattr__(name):
@@ -46,6 +47,9 @@ def __getattr__(name):
     if name in ("cluster_stats", "ClusterStats", "surface_elements", "SurfaceElements"):
         from . import stats
         return getattr(stats, name)
+    if name in ("height_grid", "HeightGrid"):
+        from . import grid
+        return getattr(grid, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

@@ -15,7 +15,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 SO_PATH = os.environ.get("PCM_SO") or os.path.join(PKG_DIR, "libpcmkm.so")
 UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in ("pcm_engine.hip", "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip",
-                                                            "pcm_xchg.hip", "pcm_stats.hip")]
+                                                            "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip")]
 SOURCES = UNITS + [os.path.join(PKG_DIR, "csrc", h) for h in ("pcm_kernels.hpp", "pcm_kpp.hpp", "pcm_sort.hpp", "pcm_cloud.hpp",
                                                               "pcm_common.hpp", "pcm_debug.hpp", "pcm_xchg.hpp")] + \
     [os.path.join(REPO_DIR, "include", "pcm_kmeans.h")]
@@ -38,11 +38,13 @@ EXPORTS = [
     "pcm_xchg_create", "pcm_xchg_destroy", "pcm_xchg_handle", "pcm_xchg_open", "pcm_xchg_link", "pcm_xchg_allreduce",
     "pcm_xchg_status", "pcm_iter_exchange", "pcm_sole_tiles",
     "pcm_predict_workspace", "pcm_predict", "pcm_dense_predict", "pcm_dense_transform",
-    "pcm_cluster_stats",
+    "pcm_cluster_stats", "pcm_height_grid",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
 STATS_MAXG = 256         # PCM_STATS_MAXG
+GRID_WORDS = 4           # PCM_GRID_WORDS
+GRID_MAXG = 256          # PCM_GRID_MAXG
 
 
 def stats_words(d: int) -> int:
@@ -192,6 +194,7 @@ def _declare(lib):
         "pcm_dense_predict": ([P, I, I64, I, P, I, P, P, P, ctypes.POINTER(PcmInertia), P, ctypes.c_size_t, P], I),
         "pcm_dense_transform": ([P, I, I64, I, P, I, P, P], I),
         "pcm_cluster_stats": ([P, I, I64, I, P, P, I, I, P, P, P], I),
+        "pcm_height_grid": ([P, I64, P, I, P, I, I, I, ctypes.c_float, ctypes.c_float, I, I, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

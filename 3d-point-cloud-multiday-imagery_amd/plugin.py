@@ -136,9 +136,68 @@ def _describe(X: np.ndarray, labels: np.ndarray, sizes, k: int, Xdev, stats: Opt
     return ClusterStats(np.asarray(words), fixed_q(np.abs(X).max(axis=0)), 3)
 
 
+GRID_LIMIT_BYTES = 1 << 32     # the words of a fused height map: 32 B per (cloud, pixel)
+
+
+def _gpu_grid(X, labels: np.ndarray, groups: np.ndarray, k: int, n_groups: int, shape, cell_log2: int, q: int):
+    """X: host (N, 3) float32 array, or the cloud already on the device -> the words (G, 4, H, W) as NumPy
+    and the number of rows outside the raster (origin (0, 0))."""
+    import torch
+
+    from .grid import height_grid
+
+    with _gpu_lock:
+        Xt = X.to(torch.float32).contiguous() if isinstance(X, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+        hg = height_grid(Xt, shape, cell_log2=cell_log2, q=q, n_clusters=k, n_groups=n_groups,
+                         labels=torch.from_numpy(np.ascontiguousarray(labels, dtype=np.int32)).to(Xt.device),
+                         groups=torch.from_numpy(np.ascontiguousarray(groups, dtype=np.uint8)).to(Xt.device))
+        return hg.numpy(), hg.outside
+
+
+def _height_map(X: np.ndarray, labels: np.ndarray, centers: np.ndarray, sizes, k: int, s: int, Xdev,
+                grid: Optional[Callable]):
+    """One ``height_grid`` pass over the labelled fused cloud (group = cloud index) -> (image layers, dict)."""
+    from .grid import HeightGrid
+    s = int(s)
+    if not -8 <= s <= 16:
+        raise ValueError(f"height_map_cell_log2 must be -8..16, got {s}")
+    G = len(sizes)
+    # origin (0, 0): the last cell that holds a point, floor(max / 2^s), in the kernel's float32
+    far = np.floor(np.ldexp(X[:, 1:].max(axis=0), -s))
+    H, W = (max(1, int(v) + 1) for v in far)
+    if G * 4 * H * W * 8 > GRID_LIMIT_BYTES or H > 1 << 24 or W > 1 << 24:
+        raise ValueError(f"fused height map of {G} clouds on {H} x {W} cells needs {G * 32 * H * W / 2 ** 30:.1f} GiB "
+                         f"of words (limit 4 GiB): raise height_map_cell_log2 (now {s})")
+    q = fixed_q([np.abs(X[:, 0]).max()])[0]
+    groups = np.repeat(np.arange(G, dtype=np.uint8), sizes)
+    words, outside = (grid or _gpu_grid)(Xdev, np.asarray(labels, dtype=np.int32), groups, k, G, (H, W), s, q)
+    hg = HeightGrid(np.asarray(words), q, s, (0.0, 0.0), outside)
+    one = hg.merged()
+    present = hg.counts() > 0                                       # (G, H, W)
+    mz = hg.means()                                                 # NaN where a cloud has no point
+    with np.errstate(invalid="ignore"):
+        spread = np.where(present.sum(0) >= 2, np.fmax.reduce(mz, axis=0) - np.fmin.reduce(mz, axis=0), 0.0)
+    top = one.top_labels()[0]
+    surface = np.where(top >= 0, np.asarray(centers, dtype=np.float64)[np.maximum(top, 0), 0], np.nan)
+    scale = (2.0 ** s, 2.0 ** s)
+    image = {"colormap": "turbo", "scale": scale}
+    layers = [
+        (one.means()[0], {"name": f"{PREFIX} Fused Height Map", **image}, "image"),
+        (np.nan_to_num(spread, nan=0.0), {"name": f"{PREFIX} Fused Height Spread", **image}, "image"),
+        (present.sum(0).astype(np.int32), {"name": f"{PREFIX} Fused Coverage", **image,
+                                           "contrast_limits": [0, G]}, "image"),
+        (surface, {"name": f"{PREFIX} Fused Surface Height", **image}, "image"),
+        ((top + 1).astype(np.int32), {"name": f"{PREFIX} Fused Surface Elements", "scale": scale}, "labels"),
+    ]
+    return layers, dict(words=hg.numpy(), q=q, cell_log2=s, origin=(0.0, 0.0), shape=(H, W), outside=int(outside),
+                        sizes=list(sizes))
+
+
 def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                 seed: int = 1, fit: Optional[Callable] = None, init: str = "rows", device_clouds=None,
-                export_path=None, describe: bool = False, stats: Optional[Callable] = None):
+                export_path=None, describe: bool = False, stats: Optional[Callable] = None,
+                height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None):
     """Fuse per-pair (M_i, 3) z,y,x clouds into one K-means reconstruction.
 
     Returns (layers, result) where ``result`` has labels (N,), centers (K, 3),
@@ -158,12 +217,28 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     mean z on the element, 0 with fewer than two); ``result`` gains ``stats`` =
     dict(words (G, K, 16) int64, q, sizes).  ``stats`` lets tests substitute
     (X, labels, groups, k, G) -> words.
+
+    ``height_map=True`` adds one exact raster pass over the labelled cloud
+    (``height_grid``; group = cloud index, at most 256; origin (0, 0), cells of
+    2^``height_map_cell_log2`` pixels, the shape reaching the largest y and x) and
+    appends four image layers and a labels layer, all with ``scale`` (2^s, 2^s):
+    "Fused Height Map" (mean z of all clouds per pixel, NaN where empty), "Fused
+    Height Spread" (max - min over the clouds of each cloud's mean z, 0 with fewer
+    than two), "Fused Coverage" (clouds seen in the pixel), "Fused Surface Height"
+    (the z of the centre whose point is the highest in the pixel: the model's
+    surface) and "Fused Surface Elements" (that centre's index + 1, 0 = background);
+    ``result`` gains ``height_map`` = dict(words (G, 4, H, W) int64, q, cell_log2,
+    origin, shape, outside, sizes).  Raises ValueError naming
+    ``height_map_cell_log2`` when the words would exceed 4 GiB.  ``grid`` lets tests
+    substitute (X, labels, groups, k, G, shape, cell_log2, q) -> (words, outside).
     """
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to fuse")
     if describe and len(clouds) > 256:
         raise ValueError(f"describe=True takes at most 256 clouds (groups), got {len(clouds)}")
+    if height_map and len(clouds) > 256:
+        raise ValueError(f"height_map=True takes at most 256 clouds (groups), got {len(clouds)}")
     X = np.concatenate(clouds).astype(np.float32)          # boundary cast (SURVEY.md a4)
     Xfit = X
     if device_clouds is not None and fit is None:
@@ -207,6 +282,11 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     result = dict(labels=labels, centers=centers, inertia=inertia, n_iter=n_iter, n_points=n)
     if st is not None:
         result["stats"] = dict(words=st.numpy(), q=list(st.q), sizes=sizes)
+    if height_map:
+        more, result["height_map"] = _height_map(X, labels, centers, [c.shape[0] for c in clouds], k,
+                                                 height_map_cell_log2,
+                                                 Xfit if (grid is None and Xfit is not X) else X, grid)
+        layers += more
     if export_path is not None:
         export_fused(export_path, X.astype(np.float64), result)
     return layers, result
@@ -295,7 +375,8 @@ class HeightMapExtractor(SatellitePlugin):
     def __init__(self, base=None, n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                  fit: Optional[Callable] = None, init: str = "rows", seed: int = 1, stages=None,
                  export_path=None, _assemble: Optional[Callable] = None, model=None,
-                 assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None):
+                 assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None,
+                 height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None):
         self._base = base
         # model: a fitted model (kmeans_fuse result, load_fused dict or export_fused path); when given,
         # run fuses nothing and labels the run's clouds against it (kmeans_assign)
@@ -304,6 +385,10 @@ class HeightMapExtractor(SatellitePlugin):
         # describe: add the per-element statistics (kmeans_fuse / kmeans_assign describe=True); stats: test stand-in
         self.describe = describe
         self._stats = stats
+        # height_map: append the fused raster layers (kmeans_fuse height_map=True); grid: test stand-in
+        self.height_map = height_map
+        self.height_map_cell_log2 = height_map_cell_log2
+        self._grid = grid
         self._stages = stages
         self.export_path = export_path
         self._assemble = _assemble   # tests: a CPU stand-in for the GPU assembly (disparity, validity) -> (pts, h_norm)
@@ -349,7 +434,8 @@ class HeightMapExtractor(SatellitePlugin):
                                               fit=self._fit, init=self.init,
                                               device_clouds=dev_clouds if use_dev else None,
                                               export_path=self.export_path, describe=self.describe,
-                                              stats=self._stats)
+                                              stats=self._stats, height_map=self.height_map,
+                                              height_map_cell_log2=self.height_map_cell_log2, grid=self._grid)
         return layers + fused
 
     def _stages_run(self, kml_path, is_debug_mode, is_debug_pair, is_one_random_pair, n) -> List:
@@ -390,7 +476,9 @@ class HeightMapExtractor(SatellitePlugin):
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path,
-                                                  describe=self.describe, stats=self._stats)
+                                                  describe=self.describe, stats=self._stats,
+                                                  height_map=self.height_map,
+                                                  height_map_cell_log2=self.height_map_cell_log2, grid=self._grid)
             return layers + fused
         except Exception as e:   # reference convention: an error layer, never an exception
             import traceback

@@ -295,6 +295,51 @@ int pcm_cluster_stats(const void *X, int dtype, int64_t n, int d,
                       uint64_t *out /* device, n_groups*k*W + 1 words, ACCUMULATED: caller zeroes */,
                       void *stream);
 
+/* ---------------------------------------------------------------- height grid
+ * Exact height-map raster of a (labelled, multi-day) cloud, in one pass over
+ * the rows in the caller's order (no reference counterpart: the reference
+ * rasters one pair and never fuses days; DESIGN.md §4 "Height grid").
+ * X: device float32 n*3 rows (z, y, x), the plugin's column order; labels
+ * (nullable: every row label 0): device int32[n], valid in [0, k); groups
+ * (nullable: every row in group 0): device uint8[n], the day / cloud of each
+ * row; H, W: the raster; (oy, ox): its origin; cell_log2 = s: a cell is 2^s
+ * units on a side, -8 <= s <= 16; q: the fixed-point exponent of z
+ * (fixed.fixed_q of max |z|).
+ * In float32 (one rounded subtraction, an exact scaling, a floor)
+ *   fy = floorf(ldexpf(y - oy, -s)),  fx = floorf(ldexpf(x - ox, -s)),
+ * the row is inside iff 0 <= fy < H and 0 <= fx < W (compared as floats), and
+ *   zq = trunc(ldexp(z, q))           (the engine's fixed point).
+ * Word w of group g is the H x W plane at out + (g*4 + w)*H*W, the pixel at
+ * fy*W + fx inside it.  An inside row updates the four words of its (g, pixel):
+ *   word 0   += 1                                            (count)
+ *   word 1   += zq                    (int64 two's complement, wrapping add)
+ *   word 2   = max(word 2, ((uint64)(zq + 2^25) << 32) | (0xffffffff - label))   (top)
+ *   word 3   = max(word 3, ((uint64)(2^25 - zq) << 32) | (0xffffffff - label))   (bottom)
+ * (unsigned 64-bit maxima).  A zero word 2 / 3 means no row: a zeroed buffer
+ * is the empty grid.  Among rows of equal height the smaller label wins.
+ * After the planes come two words: out[n_groups*4*H*W] counts the valid rows
+ * outside the raster, out[n_groups*4*H*W + 1] the skipped rows -- a row with a
+ * non-finite coordinate, a label outside [0, k), a group >= n_groups or
+ * |zq| >= 2^25 updates nothing else.
+ * The sums are EXACT while fewer than 2^31 rows in total have been accumulated
+ * into one `out`.  Adds and maxima of integers commute, so the words are the
+ * same bit pattern for any order of the rows, any grid, and any split of the
+ * rows over calls or ranks (add words 0-1, take the maximum of words 2-3).
+ * out: device uint64[n_groups*4*H*W + 2], ACCUMULATED -- the caller zeroes it.
+ * Stream-ordered: no host synchronisation, no allocation.  The arguments are
+ * checked before any device call (PCM_E_ARG: n < 0, n >= 2^31, H or W outside
+ * 1..2^24, n_groups outside 1..PCM_GRID_MAXG, n_groups*H*W >= 2^31, k < 1,
+ * cell_log2 outside -8..16, a null X or out with n > 0); n = 0 succeeds
+ * without any device call. */
+#define PCM_GRID_WORDS 4
+#define PCM_GRID_MAXG 256
+int pcm_height_grid(const float *X, int64_t n,
+                    const int32_t *labels /* nullable: all label 0 */, int k,
+                    const uint8_t *groups /* nullable: all group 0 */, int n_groups,
+                    int H, int W, float oy, float ox, int cell_log2, int q,
+                    uint64_t *out /* device, n_groups*4*H*W + 2 words, ACCUMULATED: caller zeroes */,
+                    void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
