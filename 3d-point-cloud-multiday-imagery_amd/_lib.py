@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 import threading
 
@@ -16,9 +17,32 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 SO_PATH = os.environ.get("PCM_SO") or os.path.join(PKG_DIR, "libpcmkm.so")
 UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in ("pcm_engine.hip", "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip",
                                                             "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip")]
-SOURCES = UNITS + [os.path.join(PKG_DIR, "csrc", h) for h in ("pcm_kernels.hpp", "pcm_kpp.hpp", "pcm_sort.hpp", "pcm_cloud.hpp",
-                                                              "pcm_common.hpp", "pcm_debug.hpp", "pcm_xchg.hpp")] + \
-    [os.path.join(REPO_DIR, "include", "pcm_kmeans.h")]
+
+
+def _deps(path, seen):
+    """`path` and every project header it includes, directly or not (the `#include "..."` scan)."""
+    if path in seen or not os.path.exists(path):
+        return seen
+    seen.add(path)
+    for h in re.findall(r'#include\s+"([^"]+)"', open(path).read()):
+        for d in (os.path.dirname(path), os.path.join(REPO_DIR, "include")):
+            if os.path.exists(os.path.join(d, h)):
+                _deps(os.path.join(d, h), seen)
+                break
+    return seen
+
+
+def sources():
+    """Every file the library is built from: the units and what they include."""
+    seen = set()
+    for u in UNITS:
+        _deps(u, seen)
+    return sorted(seen)
+
+
+SOURCES = sources()   # as of import; needs_build() scans again
+
+
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared"]
 
@@ -76,7 +100,7 @@ def needs_build() -> bool:
     if not os.path.exists(SO_PATH):
         return True
     t = os.path.getmtime(SO_PATH)
-    return any(os.path.getmtime(s) > t for s in SOURCES if os.path.exists(s))
+    return any(os.path.getmtime(s) > t for s in sources())
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -87,28 +111,16 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # object cache (the ignored build/ beside the sources: two checkouts never
     # share objects; a unit is rebuilt when it or a header it includes is newer
     # than its object), then one link
-    import re
     from concurrent.futures import ThreadPoolExecutor
     inc = ["-I", os.path.join(REPO_DIR, "include")]
     objdir = os.environ.get("PCM_OBJ_DIR") or os.path.join(PKG_DIR, "build")
     os.makedirs(objdir, exist_ok=True)
 
-    def deps(path, seen):
-        if path in seen or not os.path.exists(path):
-            return seen
-        seen.add(path)
-        for h in re.findall(r'#include\s+"([^"]+)"', open(path).read()):
-            for d in (os.path.dirname(path), os.path.join(REPO_DIR, "include")):
-                if os.path.exists(os.path.join(d, h)):
-                    deps(os.path.join(d, h), seen)
-                    break
-        return seen
-
     objs, cmds = [], []
     for u in UNITS:
         o = os.path.join(objdir, os.path.basename(u) + ".o")
         objs.append(o)
-        if force or not os.path.exists(o) or any(os.path.getmtime(d) > os.path.getmtime(o) for d in deps(u, set())):
+        if force or not os.path.exists(o) or any(os.path.getmtime(d) > os.path.getmtime(o) for d in _deps(u, set())):
             cmds.append([HIPCC, *HIP_FLAGS[:-1], *inc, "-c", u, "-o", o])
     if verbose:
         print("\n".join(" ".join(c) for c in cmds))

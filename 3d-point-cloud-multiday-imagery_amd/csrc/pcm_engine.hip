@@ -73,7 +73,7 @@ struct pcm_engine {
     bool use_xz = false;             // the current layout has a compressed stream
     bool tiles_lpt = false;          // tiles ordered longest candidate list first (PCM_TILE_LPT, A/B)
     size_t cap_xz = 0, cap_tmeta = 0;
-    // sole-owner tiles (SoleW, pcm_kernels.hpp): a tile whose cell has a one-entry list adds tsum, unread
+    // sole-owner tiles (SoleW, pcm_cand.hpp): a tile whose cell has a one-entry list adds tsum, unread
     long long *tsum = nullptr;       // [tile][d] fixed-point coordinate sums of the tile's points
     uint32_t *tpos = nullptr;        // reordered tiles: layout tile index -> current position
     uint32_t *torig = nullptr;       // ... and its inverse
@@ -147,11 +147,7 @@ const int BBOX_BLOCKS = 1024;
 size_t tsize(int dtype) { return dtype == PCM_F16 ? 2 : 4; }
 
 // Internal sorted-order labels are uint16 when every label fits (saves 4 B/pt/iter of HBM).
-#ifdef PCM_DBG_LABEL32
-bool small_labels(const pcm_engine *) { return false; }
-#else
 bool small_labels(const pcm_engine *e) { return e->k <= 65535; }
-#endif
 size_t lsize(const pcm_engine *e) { return small_labels(e) ? 2 : 4; }
 
 int check_device(pcm_engine *e) {
@@ -1704,7 +1700,7 @@ int pcm_synth_uniform(float *out, int64_t n, int d, uint64_t seed, int64_t start
 }
 
 // Debug (not in the public header): copy the sorted layout to device buffers
-// (xs in the AoSoA-4 order of pcm_kernels.hpp xs_index).
+// (xs in the AoSoA-4 order of pcm_layout.hpp xs_index).
 int pcm_debug_layout(pcm_engine *e, void *xs_out, int32_t *lab_out, uint32_t *perm_out, void *stream) {
     if (!e || !e->layout_ready) return fail(PCM_E_STATE, "layout not built");
     hipStream_t s = (hipStream_t)stream;

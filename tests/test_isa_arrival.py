@@ -1,6 +1,6 @@
 """CPU: ISA check of k_updlists' early-issued arrival.
 
-``arrive_issue`` (csrc/pcm_kernels.hpp) is an inline-asm ``global_atomic_add
+``arrive_issue`` (csrc/pcm_kcommon.hpp) is an inline-asm ``global_atomic_add
 ... sc0`` whose returned value stays in flight through the block's list work
 until ``arrive_read``'s explicit ``s_waitcnt vmcnt(0)`` + ``v_readfirstlane``.
 hipcc's waitcnt pass does not see the asm, so nothing but the generated code
