@@ -15,8 +15,10 @@ import threading
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO_DIR = os.path.dirname(PKG_DIR)
 SO_PATH = os.environ.get("PCM_SO") or os.path.join(PKG_DIR, "libpcmkm.so")
-UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in ("pcm_engine.hip", "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip",
-                                                            "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip")]
+UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
+    # the Lloyd engine's host units ("Host units"), the slowest to compile first
+    "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
+    "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip")]
 
 
 def _deps(path, seen):

@@ -282,7 +282,7 @@ __device__ __forceinline__ void inert_flush(unsigned long long lo, unsigned long
 }
 
 // inert[0..3] += the replica sums; replicas := 0 (one 64-thread block)
-__global__ void k_inert_fold(unsigned long long *__restrict__ rep, unsigned long long *__restrict__ inert) {
+inline __global__ void k_inert_fold(unsigned long long *__restrict__ rep, unsigned long long *__restrict__ inert) {
     const int q = threadIdx.x;
     if (q >= 4) return;
     unsigned long long v = 0ull;

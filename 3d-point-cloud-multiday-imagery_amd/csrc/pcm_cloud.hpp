@@ -21,7 +21,7 @@ namespace pcm {
 
 constexpr int CLOUD_TPB = 256;
 
-__global__ __launch_bounds__(CLOUD_TPB) void k_cloud_flags(const double *__restrict__ disp,
+inline __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_flags(const double *__restrict__ disp,
                                                            const uint8_t *__restrict__ validity, long long n,
                                                            double limit, uint32_t *__restrict__ flags,
                                                            double *__restrict__ height) {
@@ -33,7 +33,7 @@ __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_flags(const double *__restr
     height[i] = h;
 }
 
-__global__ __launch_bounds__(CLOUD_TPB) void k_cloud_compact(const uint32_t *__restrict__ flags,
+inline __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_compact(const uint32_t *__restrict__ flags,
                                                              const uint32_t *__restrict__ pos,
                                                              const double *__restrict__ height, long long n,
                                                              long long W, double *__restrict__ P) {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_sums(const double *__restri
     }
 }
 
-__global__ __launch_bounds__(CLOUD_TPB) void k_cloud_project(const double *__restrict__ P, long long m, double cx,
+inline __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_project(const double *__restrict__ P, long long m, double cx,
                                                              double cy, double cz, double n0, double n1, double n2,
                                                              double *__restrict__ zrel) {
     const long long j = blockIdx.x * (long long)CLOUD_TPB + threadIdx.x;
@@ -86,7 +86,7 @@ __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_project(const double *__res
     zrel[j] = ((P[3 * j] - cx) * n0 + (P[3 * j + 1] - cy) * n1) + (P[3 * j + 2] - cz) * n2;
 }
 
-__global__ __launch_bounds__(CLOUD_TPB) void k_cloud_output(const double *__restrict__ P,
+inline __global__ __launch_bounds__(CLOUD_TPB) void k_cloud_output(const double *__restrict__ P,
                                                             const double *__restrict__ zrel, long long m,
                                                             double h_min, double h_max,
                                                             double *__restrict__ points,

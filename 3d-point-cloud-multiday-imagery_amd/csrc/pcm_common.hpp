@@ -1,4 +1,5 @@
-// pcm_common.hpp — helpers shared by the translation units of libpcmkm.so.
+// pcm_common.hpp — helpers shared by every translation unit of libpcmkm.so (the Lloyd engine's
+// host units share more: pcm_host.hpp).
 #pragma once
 #include <string>
 

@@ -4,7 +4,7 @@
 // KMeans(n_clusters=5, random_state=42, n_init=10).fit_predict(StandardScaler(X))
 // on ~1500 x 20 float64 superpixel features.
 //
-// The point-cloud engine (pcm_engine.hip) prunes candidates on a D <= 4 grid;
+// The point-cloud engine (pcm_engine.hip, pcm_layout.hip) prunes candidates on a D <= 4 grid;
 // feature vectors (D up to PCM_DENSE_DMAX) have no useful grid, so this path is
 // brute force over all K (centres staged in LDS) and computes in the INPUT
 // precision (float64 stays float64, like scikit-learn).  Canonical arithmetic

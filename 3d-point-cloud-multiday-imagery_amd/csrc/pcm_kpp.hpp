@@ -29,7 +29,7 @@
 // steps, with gmax large, are full passes).  Potentials are exact unsigned
 // integers: the sampled indices are the oracle's for any launch geometry.
 #pragma once
-#include "pcm_kernels.hpp"
+#include "pcm_layout.hpp"   // xs_index
 
 namespace pcm {
 

@@ -9,7 +9,7 @@ struct ZeroSpans {
     unsigned long long *p[4];
     long long n[4];
 };
-__global__ __launch_bounds__(256) void k_zero_spans(ZeroSpans z) {
+inline __global__ __launch_bounds__(256) void k_zero_spans(ZeroSpans z) {
     const long long st = (long long)gridDim.x * blockDim.x;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -145,7 +145,7 @@ template <typename T, int D> struct PRec {
 };
 
 // cell_start[c] = sub_start[c << d], c in [0, ncells]
-__global__ __launch_bounds__(256) void k_cell_from_sub(const uint32_t *__restrict__ sub_start, long long ncells, int d,
+inline __global__ __launch_bounds__(256) void k_cell_from_sub(const uint32_t *__restrict__ sub_start, long long ncells, int d,
                                                        uint32_t *__restrict__ cell_start) {
     long long c = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (c <= ncells) cell_start[c] = sub_start[c << d];
@@ -160,7 +160,7 @@ __device__ __forceinline__ long long xs_index(long long i, int a) {
     return ((i >> 2) * D + a) * 4 + (i & 3);
 }
 
-__global__ __launch_bounds__(256) void k_tile_counts(const uint32_t *__restrict__ start, long long ncells,
+inline __global__ __launch_bounds__(256) void k_tile_counts(const uint32_t *__restrict__ start, long long ncells,
                                                      uint32_t *__restrict__ cnt, uint32_t cap) {
     long long c = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (c >= ncells) return;
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void k_tile_counts(const uint32_t *__restrict_
 }
 
 // tile_off[nc] and the tile count (the scan is exclusive: add the last cell's count)
-__global__ void k_tile_total(uint32_t *__restrict__ off, const uint32_t *__restrict__ cnt, long long ncells,
+inline __global__ void k_tile_total(uint32_t *__restrict__ off, const uint32_t *__restrict__ cnt, long long ncells,
                              uint32_t *__restrict__ ntiles) {
     if (threadIdx.x != 0) return;
     const uint32_t t = off[ncells - 1] + cnt[ncells - 1];
@@ -177,7 +177,7 @@ __global__ void k_tile_total(uint32_t *__restrict__ off, const uint32_t *__restr
     *ntiles = t;
 }
 
-__global__ __launch_bounds__(256) void k_tile_write(const uint32_t *__restrict__ start, const uint32_t *__restrict__ off,
+inline __global__ __launch_bounds__(256) void k_tile_write(const uint32_t *__restrict__ start, const uint32_t *__restrict__ off,
                                                     long long ncells, uint4 *__restrict__ tiles, uint32_t cap) {
     long long c = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (c >= ncells) return;
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_tile_write(const uint32_t *__restrict__
 // Longest-list-first tile order (pcm_fit_begin): key = 0xffff - the list
 // length of the tile's cell at the first lists (FULL: the longest), value = the
 // tile; a stable radix sort, then the records gathered in that order.
-__global__ __launch_bounds__(256) void k_tile_lpt_keys(const uint4 *__restrict__ tiles, const uint32_t *__restrict__ fc_cnt,
+inline __global__ __launch_bounds__(256) void k_tile_lpt_keys(const uint4 *__restrict__ tiles, const uint32_t *__restrict__ fc_cnt,
                                                        unsigned nt, uint32_t *__restrict__ key, uint32_t *__restrict__ idx) {
     const unsigned t = blockIdx.x * 256u + threadIdx.x;
     if (t >= nt) return;
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(256) void k_tile_lpt_keys(const uint4 *__restrict__
 // (tile_off[cell] + i) to its current position is kept: torig (position ->
 // layout index; null = identity, the first reorder of a layout) is permuted,
 // tpos (its inverse) rewritten.
-__global__ __launch_bounds__(256) void k_tile_gather(const uint4 *__restrict__ tiles, const uint4 *__restrict__ tmeta,
+inline __global__ __launch_bounds__(256) void k_tile_gather(const uint4 *__restrict__ tiles, const uint4 *__restrict__ tmeta,
                                                      const uint32_t *__restrict__ idx, unsigned nt,
                                                      uint4 *__restrict__ t2, uint4 *__restrict__ m2,
                                                      const long long *__restrict__ tsum, long long *__restrict__ s2, int d,
@@ -254,7 +254,7 @@ __device__ __forceinline__ unsigned zwidth(unsigned span) { return span ? 32u - 
 constexpr unsigned ZHI = 256;
 __host__ __device__ __forceinline__ size_t zword(size_t i) { return (i >> 8) * 512u + (i & 255u); }
 
-__global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__ xs, const uint4 *__restrict__ tiles,
+inline __global__ __launch_bounds__(256) void k_tile_compress(const float *__restrict__ xs, const uint4 *__restrict__ tiles,
                                                        const uint32_t *__restrict__ ntiles, uint4 *__restrict__ tmeta,
                                                        unsigned *__restrict__ xz, unsigned long long *__restrict__ zpts,
                                                        QExp qe, long long *__restrict__ tsum) {
@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void k_zsample(const T *__restrict__ X, long l
     atomicAdd(counts + encode(idx, g.G, D), 1u);
 }
 
-__global__ __launch_bounds__(256) void k_umax(const uint32_t *__restrict__ v, long long n, uint32_t *__restrict__ out) {
+inline __global__ __launch_bounds__(256) void k_umax(const uint32_t *__restrict__ v, long long n, uint32_t *__restrict__ out) {
     uint32_t m = 0;
     for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         m = max(m, v[i]);
@@ -561,7 +561,7 @@ __global__ __launch_bounds__(256) void k_tile_cand(const uint4 *__restrict__ til
 // tile list, out[2] += the lengths of those lists; out[3] += tile lists longer
 // than TLCAP (k_lloyd1 scans them through LDS chunks), out[4] += all-K tiles (a
 // FULL cell whose tile got no list either), out[5] = the longest tile list.
-__global__ __launch_bounds__(256) void k_tile_list_stats(const uint4 *__restrict__ tiles,
+inline __global__ __launch_bounds__(256) void k_tile_list_stats(const uint4 *__restrict__ tiles,
                                                          const uint32_t *__restrict__ ntiles,
                                                          const uint32_t *__restrict__ fc_cnt,
                                                          const uint32_t *__restrict__ tl_cnt,

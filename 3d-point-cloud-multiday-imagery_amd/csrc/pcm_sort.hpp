@@ -19,7 +19,7 @@
 // Reads/writes per point at config 3 (fp32 D = 3, 15-bit keys, 2 passes):
 // 12 (count) + 12 + 16 (scatter) + 16 (count) + 16 + 16 (scatter) = 88 B.
 #pragma once
-#include "pcm_kernels.hpp"
+#include "pcm_assign.hpp"   // xcd_block; sort_key_f, PRec, xs_index (pcm_layout.hpp)
 
 namespace pcm {
 
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(RS_CTPB) void k_rs_count(const T *__restrict__ X, c
 // chunks and all smaller digits) = where chunk's first item of digit d goes.
 constexpr int RS_SEG = 256;
 
-__global__ __launch_bounds__(RS_DIG) void k_rs_colscan(const uint32_t *__restrict__ hist, long long nblk,
+inline __global__ __launch_bounds__(RS_DIG) void k_rs_colscan(const uint32_t *__restrict__ hist, long long nblk,
                                                        uint32_t *__restrict__ goff, uint32_t *__restrict__ segt) {
     const int t = threadIdx.x;
     const long long r0 = (long long)blockIdx.x * RS_SEG, r1 = min(r0 + RS_SEG, nblk);
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(RS_DIG) void k_rs_colscan(const uint32_t *__restric
 
 // One block: segment bases per digit, then every digit's global base (an
 // exclusive scan over the digits of their totals), folded into segb.
-__global__ __launch_bounds__(RS_DIG) void k_rs_segscan(uint32_t *__restrict__ segb, long long nseg) {
+inline __global__ __launch_bounds__(RS_DIG) void k_rs_segscan(uint32_t *__restrict__ segb, long long nseg) {
     __shared__ uint32_t wtot[RS_DIG / 64];
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
     uint32_t acc = 0u;

@@ -38,7 +38,7 @@ struct RselState {
 };
 
 // Histogram of byte `pass` (0 = most significant) of the keys whose higher bytes equal the prefix.
-__global__ __launch_bounds__(256) void k_rsel_hist(const unsigned long long *__restrict__ keys, long long n,
+inline __global__ __launch_bounds__(256) void k_rsel_hist(const unsigned long long *__restrict__ keys, long long n,
                                                    RselState *__restrict__ st, int pass) {
     __shared__ unsigned int h[256];
     h[threadIdx.x] = 0u;
@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void k_rsel_hist(const unsigned long long *__r
 }
 
 // One thread: the byte value holding the m_rem-th largest matching key.
-__global__ void k_rsel_pick(RselState *__restrict__ st, int pass) {
+inline __global__ void k_rsel_pick(RselState *__restrict__ st, int pass) {
     if (threadIdx.x != 0) return;
     unsigned long long above = 0ull;
     int v = 255;
@@ -175,7 +175,7 @@ __global__ __launch_bounds__(256) void k_unpermute_win(const LT *__restrict__ la
 }
 
 // uint16 row-order labels -> int32 (0xffff stays -1 only where K > 65535, which never takes this path)
-__global__ __launch_bounds__(256) void k_widen_u16(const uint16_t *__restrict__ in, long long n, int32_t *__restrict__ out) {
+inline __global__ __launch_bounds__(256) void k_widen_u16(const uint16_t *__restrict__ in, long long n, int32_t *__restrict__ out) {
     long long i = (blockIdx.x * (long long)blockDim.x + threadIdx.x) * 4;
     if (i + 4 <= n) {
         const uint2 w = *reinterpret_cast<const uint2 *>(in + i);
@@ -202,7 +202,7 @@ __global__ void k_centers_out(const float4 *__restrict__ C, int K, float *__rest
     for (int a = 0; a < D; ++a) out[(size_t)j * D + a] = comp(c, a);
 }
 
-__global__ __launch_bounds__(256) void k_fill_i32(int32_t *__restrict__ p, long long n, int32_t v) {
+inline __global__ __launch_bounds__(256) void k_fill_i32(int32_t *__restrict__ p, long long n, int32_t v) {
     long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (i < n) p[i] = v;
 }
@@ -215,14 +215,14 @@ __device__ __forceinline__ float synth_value(unsigned long long ctr, unsigned lo
     return (float)(uint32_t)(z >> 40) * 5.9604644775390625e-08f;
 }
 
-__global__ __launch_bounds__(256) void k_synth(float *__restrict__ out, long long n, int d, unsigned long long seed,
+inline __global__ __launch_bounds__(256) void k_synth(float *__restrict__ out, long long n, int d, unsigned long long seed,
                                                long long start) {
     long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (e >= n * d) return;
     out[e] = synth_value((unsigned long long)(start * d + e), seed);
 }
 
-__global__ __launch_bounds__(256) void k_synth_rows(float *__restrict__ out, const long long *__restrict__ rows,
+inline __global__ __launch_bounds__(256) void k_synth_rows(float *__restrict__ out, const long long *__restrict__ rows,
                                                     long long m, int d, unsigned long long seed) {
     long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (e >= m * d) return;
@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_synth_rows(float *__restrict__ out, con
 }
 
 // Candidate-list statistics for diagnostics.
-__global__ __launch_bounds__(256) void k_cand_stats(const uint32_t *__restrict__ fc_cnt, long long ncells,
+inline __global__ __launch_bounds__(256) void k_cand_stats(const uint32_t *__restrict__ fc_cnt, long long ncells,
                                                     unsigned long long *__restrict__ out /* sum, max, full */) {
     long long c = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (c >= ncells) return;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_cand_stats(const uint32_t *__restrict__
 }
 
 // Sole-owner tiles (owner word set) and their points, for diagnostics.
-__global__ __launch_bounds__(256) void k_sole_stats(const uint4 *__restrict__ tiles, const uint32_t *__restrict__ ntiles,
+inline __global__ __launch_bounds__(256) void k_sole_stats(const uint4 *__restrict__ tiles, const uint32_t *__restrict__ ntiles,
                                                     unsigned long long *__restrict__ out /* tiles, points */) {
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     const uint4 tr = t < (long long)*ntiles ? tiles[t] : make_uint4(0u, 0u, 0u, 0u);
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256) void k_bruteforce(const float *__restrict__ X,
 
 // ------------------------------------------------------------------ predict
 // Centres (K, D) float32 -> the float4 records the list builders and the scans read.
-__global__ __launch_bounds__(256) void k_predict_pack(const float *__restrict__ Cg, int K, int D,
+inline __global__ __launch_bounds__(256) void k_predict_pack(const float *__restrict__ Cg, int K, int D,
                                                       float4 *__restrict__ C4) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= K) return;

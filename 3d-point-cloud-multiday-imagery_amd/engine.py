@@ -16,7 +16,7 @@ from . import _lib
 
 PCM_F32, PCM_F16 = 0, 1
 RELOC_RECORD_BYTES = 32
-# one engine holds fewer than 2^28 - 16 padded points (pcm_engine.hip, pcm_layout_build's check);
+# one engine holds fewer than 2^28 - 16 padded points (pcm_layout.hip, pcm_layout_build's check);
 # larger clouds are sharded over engines / ranks
 ENGINE_MAX_POINTS = (1 << 28) - 4096
 

@@ -13,9 +13,9 @@ X = synth_uniform(n, d, seed=0)
 pcm_amd.kmeans_plusplus(X, k, random_state=0)
 torch.cuda.synchronize()
 lib = _lib.load()
-lib.pcm_debug_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
+lib.pcm_debug_timing_kpp.argtypes = [ctypes.c_void_p, ctypes.c_int]
 buf = np.zeros((8192, 16), np.uint64)
-assert lib.pcm_debug_timing(buf.ctypes.data_as(ctypes.c_void_p), 8192) == 0
+assert lib.pcm_debug_timing_kpp(buf.ctypes.data_as(ctypes.c_void_p), 8192) == 0
 t = buf.astype(np.int64)
 L = 2 + int(np.log(k))
 us = lambda v: v / 100.0
