@@ -223,6 +223,8 @@ int host_candidates(int d, const Grid &g, const float4 *C, int k, Ctrl *ctrl, in
 
 // pcm_layout.hip
 void make_grid(Grid &g, int d, const double *lo, const double *hi, double target);
+// Halve the axis with the most cells until ncells <= ncells_max and ncoarse <= ncoarse_max (thin boxes).
+void clamp_grid(Grid &g, long long ncells_max, long long ncoarse_max);
 int inertia_scale(const int32_t *q, int d);
 // Bounding box of the n > 0 rows of X into hb = {lo[d], hi[d]} (one stream synchronisation);
 // PCM_E_NONFINITE when a coordinate is NaN or Inf.  part: BBOX_BLOCKS * 2 * MAXD floats, out: 2 * MAXD doubles.

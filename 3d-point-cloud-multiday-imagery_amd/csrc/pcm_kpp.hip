@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <limits>
 
 #include "pcm_kpp.hpp"
 #include "pcm_host.hpp"
@@ -104,6 +105,9 @@ int pcm_kmeanspp(const float *X, int64_t n, int d, int k, int n_local_trials, in
     const int scale = kpp_scale(n, maxd);
     Grid g;
     make_grid(g, d, hb, hb + d, std::max(1.0, (double)n / KPP_CELL_PTS));
+    // a thin box (a few pixels of relief over a whole image) gets far more cells than kpp_cells_max
+    // along its long axes: clamp_grid halves them until the cell arrays fit; a grid that fits stays
+    clamp_grid(g, w.nc_max, std::numeric_limits<long long>::max());
     const long long nc = g.ncells;
     if (nc > w.nc_max) return fail(PCM_E_STATE, "kmeanspp: grid exceeds the workspace bound");
     unsigned bits = 1;

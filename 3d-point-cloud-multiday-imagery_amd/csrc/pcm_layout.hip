@@ -214,6 +214,34 @@ void pcm::make_grid(Grid &g, int d, const double *lo, const double *hi, double t
     g.prune = (maxext < 1e18) ? 1 : 0;
 }
 
+// make_grid's cell counts clamped to a caller's table bounds.  make_grid sizes
+// the cells from the box's volume and gives every axis at least one cell, so a
+// thin box (one axis far shorter than the others, yet not constant) gets far
+// more cells than the target along its long axes, whatever the target.  The
+// axis with the most cells is halved until the grid fits; that ends at the
+// latest with one cell per axis (1 cell, 1 coarse cell).  A grid that fits is
+// left as make_grid made it.  The cell count affects speed only.
+void pcm::clamp_grid(Grid &g, long long ncells_max, long long ncoarse_max) {
+    const int d = g.d;
+    while (g.ncells > ncells_max || g.ncoarse > ncoarse_max) {
+        int amax = 0;
+        for (int a = 1; a < d; ++a)
+            if (g.G[a] > g.G[amax]) amax = a;
+        if (g.G[amax] <= 1) break;   // one cell: bounds below 1 are the caller's error
+        g.G[amax] = std::max(1, g.G[amax] / 2);
+        long long nc = 1, ncc = 1;
+        for (int a = 0; a < d; ++a) {   // the derived fields, as make_grid sets them
+            g.w[a] = g.ext[a] / g.G[a];
+            g.inv[a] = g.ext[a] > 0 ? (double)g.G[a] / g.ext[a] : 0.0;
+            g.GC[a] = (g.G[a] + g.F - 1) / g.F;
+            nc *= g.G[a];
+            ncc *= g.GC[a];
+        }
+        g.ncells = nc;
+        g.ncoarse = ncc;
+    }
+}
+
 // The Lloyd engine's pruning grid: about min(32 K, n / 2800) cells -- ~2.8k
 // points per cell: fewer, fuller tiles (a tile round is 512 points) outweigh
 // the slightly longer candidate lists (swept on 12.5M / 100M clouds).

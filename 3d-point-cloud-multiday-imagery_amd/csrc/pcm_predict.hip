@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <new>
 
@@ -56,32 +57,12 @@ void pred_layout(long long n, int d, int k, PredWs &w) {
     w.total = o;
 }
 
-// make_grid over the box, then the cell counts clamped to the workspace bounds.
-// make_grid sizes the cells from the box's volume and gives every axis at least
-// one cell, so a thin box (one axis far shorter than the others, yet not
-// constant) gets far more cells than the target along its long axes, whatever
-// the target.  The axis with the most cells is halved until the grid fits; that
-// ends at the latest with one cell per axis (1 cell, 1 coarse cell, inside
-// every bound pred_layout gives).  The cell count affects speed only.
+// make_grid over the box, then the cell counts clamped to the workspace bounds
+// (clamp_grid, pcm_layout.hip: thin boxes; 1 cell and 1 coarse cell are inside
+// every bound pred_layout gives).  The coarse tables exist at D = 4 only.
 void pred_grid(Grid &g, int d, const double *lo, const double *hi, double target, const PredWs &w) {
     make_grid(g, d, lo, hi, target);
-    while (g.ncells > w.nc_max || (d >= 4 && g.ncoarse > w.ncoarse_max)) {
-        int amax = 0;
-        for (int a = 1; a < d; ++a)
-            if (g.G[a] > g.G[amax]) amax = a;
-        if (g.G[amax] <= 1) break;   // one cell: cannot happen above the bounds
-        g.G[amax] = std::max(1, g.G[amax] / 2);
-        long long nc = 1, ncc = 1;
-        for (int a = 0; a < d; ++a) {   // the derived fields, as make_grid sets them
-            g.w[a] = g.ext[a] / g.G[a];
-            g.inv[a] = g.ext[a] > 0 ? (double)g.G[a] / g.ext[a] : 0.0;
-            g.GC[a] = (g.G[a] + g.F - 1) / g.F;
-            nc *= g.G[a];
-            ncc *= g.GC[a];
-        }
-        g.ncells = nc;
-        g.ncoarse = ncc;
-    }
+    clamp_grid(g, w.nc_max, d >= 4 ? w.ncoarse_max : std::numeric_limits<long long>::max());
 }
 
 int pred_args(int64_t n, int d, int k) {

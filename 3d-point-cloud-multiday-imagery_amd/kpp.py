@@ -91,6 +91,8 @@ def kmeans_plusplus(X: torch.Tensor, n_clusters: int, *, random_state=None, n_lo
         raise ValueError(f"n_samples={n} should be >= n_clusters={k}")
     rs = random_state if isinstance(random_state, np.random.RandomState) else np.random.RandomState(random_state)
     L = 2 + int(np.log(k)) if n_local_trials is None else int(n_local_trials)
+    if L < 1:
+        raise ValueError(f"n_local_trials={L} should be >= 1")      # (pcm_kmeanspp rejects more than 16)
     u0, umant = _draws(rs, k, L)
     if weight_dtype is None:
         weight_dtype = np.float64 if X.dtype == torch.float64 else np.float32
