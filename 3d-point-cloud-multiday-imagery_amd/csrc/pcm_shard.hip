@@ -160,6 +160,8 @@ int pcm_shard_hist(const void *X, int dtype, int64_t n, int d, int axis, double 
     if ((!X && n > 0) || !hist || n < 0 || d < 1 || d > 4 || axis < 0 || axis >= d || nbins < 1 ||
         nbins > HIST_BINS_MAX)
         return pcm_fail(PCM_E_ARG, "pcm_shard_hist: bad argument");
+    // rejected before any device call, like every other argument (and like pcm_shard_partition)
+    if (dtype != PCM_F32 && dtype != PCM_F16) return pcm_fail(PCM_E_ARG, "pcm_shard_hist: dtype must be PCM_F32 or PCM_F16");
     hipStream_t s = (hipStream_t)stream;
     if (hipError_t e = hipMemsetAsync(hist, 0, (size_t)nbins * 8, s))
         return pcm_fail(PCM_E_HIP, std::string("pcm_shard_hist: ") + hipGetErrorString(e));
@@ -172,11 +174,9 @@ int pcm_shard_hist(const void *X, int dtype, int64_t n, int d, int axis, double 
     if (dtype == PCM_F32)
         k_shard_hist<float><<<g, TPB, 0, s>>>((const float *)X, n, d, axis, lo, inv, nbins,
                                               (unsigned long long *)hist);
-    else if (dtype == PCM_F16)
+    else
         k_shard_hist<__half><<<g, TPB, 0, s>>>((const __half *)X, n, d, axis, lo, inv, nbins,
                                                (unsigned long long *)hist);
-    else
-        return pcm_fail(PCM_E_ARG, "pcm_shard_hist: dtype must be PCM_F32 or PCM_F16");
     if (hipError_t e = hipGetLastError()) return pcm_fail(PCM_E_HIP, std::string("k_shard_hist: ") + hipGetErrorString(e));
     return 0;
 }
