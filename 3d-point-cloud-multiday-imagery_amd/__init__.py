@@ -20,6 +20,9 @@ kmeans_assign(clouds, model)                           -> a later day's cloud la
 cluster_stats(X, labels, n_clusters, groups=...)       -> ClusterStats: exact per-(day, cluster) counts, sums, second moments
 surface_elements(stats)                                -> per-cluster normal, roughness, planarity, rms (host, from the moments)
 height_grid(X, shape, cell_log2=, labels=, groups=...) -> HeightGrid: exact per-(day, pixel) count, height sum, top and bottom
+align_stats(X, centers, groups=, transforms=, max_dist=) -> AlignStats: exact per-day sums of the points and their nearest centres
+register_days(X, centers, groups=, kind="rigid")       -> Registration: each day's z offset, translation or rigid motion onto the centres
+apply_registration(X, registration, groups=)           -> the cloud in the centres' frame (the pass's own float32 arithmetic)
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -30,7 +33,8 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "build_library", "kmeans_plusplus", "assemble_cloud", "KMeans", "dense_fit", "dense_kmeanspp",
            "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
-           "SurfaceElements", "height_grid", "HeightGrid"]
+           "SurfaceElements", "height_grid", "HeightGrid", "align_stats", "AlignStats", "register_days", "Registration",
+           "apply_registration"]
 
 
 def __getattr__(name):
@@ -50,6 +54,9 @@ def __getattr__(name):
     if name in ("height_grid", "HeightGrid"):
         from . import grid
         return getattr(grid, name)
+    if name in ("align_stats", "AlignStats", "AlignPlan", "register_days", "Registration", "apply_registration"):
+        from . import align
+        return getattr(align, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

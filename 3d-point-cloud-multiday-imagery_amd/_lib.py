@@ -18,7 +18,7 @@ SO_PATH = os.environ.get("PCM_SO") or os.path.join(PKG_DIR, "libpcmkm.so")
 UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
     # the Lloyd engine's host units ("Host units"), the slowest to compile first
     "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
-    "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip")]
+    "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip")]
 
 
 def _deps(path, seen):
@@ -65,12 +65,15 @@ EXPORTS = [
     "pcm_xchg_status", "pcm_iter_exchange", "pcm_sole_tiles",
     "pcm_predict_workspace", "pcm_predict", "pcm_dense_predict", "pcm_dense_transform",
     "pcm_cluster_stats", "pcm_height_grid",
+    "pcm_align_workspace", "pcm_align_prepare", "pcm_align_stats", "pcm_align_apply",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
 STATS_MAXG = 256         # PCM_STATS_MAXG
 GRID_WORDS = 4           # PCM_GRID_WORDS
 GRID_MAXG = 256          # PCM_GRID_MAXG
+ALIGN_WORDS = 38         # PCM_ALIGN_WORDS
+ALIGN_MAXG = 256         # PCM_ALIGN_MAXG
 
 
 def stats_words(d: int) -> int:
@@ -91,6 +94,11 @@ class PcmStatus(ctypes.Structure):
                 ("last_shift", ctypes.c_double), ("inertia_limbs", ctypes.c_uint64 * 3),
                 ("inertia_scale", ctypes.c_int32), ("inertia_overflow", ctypes.c_uint32),
                 ("list_rebuilds", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+
+
+class PcmAlignPlan(ctypes.Structure):
+    """pcm_align_plan: the host side of a prepared registration workspace (opaque)."""
+    _fields_ = [("opaque", ctypes.c_uint64 * 64)]
 
 
 class PcmInertia(ctypes.Structure):
@@ -209,6 +217,10 @@ def _declare(lib):
         "pcm_dense_transform": ([P, I, I64, I, P, I, P, P], I),
         "pcm_cluster_stats": ([P, I, I64, I, P, P, I, I, P, P, P], I),
         "pcm_height_grid": ([P, I64, P, I, P, I, I, I, ctypes.c_float, ctypes.c_float, I, I, P, P], I),
+        "pcm_align_workspace": ([I64, I, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_align_prepare": ([P, I, I64, ctypes.c_float, P, ctypes.c_size_t, ctypes.POINTER(PcmAlignPlan), P, P], I),
+        "pcm_align_stats": ([P, I64, P, I, P, ctypes.c_float, P, P, P, P, ctypes.POINTER(PcmAlignPlan), P], I),
+        "pcm_align_apply": ([P, I64, P, I, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

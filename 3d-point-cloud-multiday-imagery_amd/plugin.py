@@ -194,10 +194,63 @@ def _height_map(X: np.ndarray, labels: np.ndarray, centers: np.ndarray, sizes, k
                         sizes=list(sizes))
 
 
+REGISTER_KINDS = ("z", "translation", "rigid")
+
+
+def _gpu_align(X: np.ndarray, C: np.ndarray, groups: np.ndarray, n_groups: int, kind: str, max_dist):
+    """Host (N, 3) float32 rows and their cloud index -> (the Registration's fields as a dict, the registered
+    rows as float32 NumPy): ``register_days`` onto the centres ``C``, then ``apply_registration``."""
+    import torch
+
+    from .align import apply_registration, register_days
+
+    with _gpu_lock:
+        Xt = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+        gt = torch.from_numpy(np.ascontiguousarray(groups, dtype=np.uint8)).to(Xt.device)
+        Ct = torch.from_numpy(np.ascontiguousarray(C, dtype=np.float32)).to(Xt.device)
+        reg = register_days(Xt, Ct, groups=gt, n_groups=n_groups, kind=kind, max_dist=max_dist)
+        out = apply_registration(Xt, reg, gt)
+        torch.cuda.synchronize()
+        return reg.as_dict(), out.cpu().numpy()
+
+
+def _register_clouds(clouds, centers: np.ndarray, fixed: Optional[int], kind: str, max_dist, align: Optional[Callable]):
+    """Register every cloud but ``fixed`` (None: every cloud) onto ``centers``; group = the cloud's index.
+    -> (the clouds in the centres' frame (float64 of the float32 the pass wrote), the registration dict
+    over ALL clouds: the fixed one keeps the identity, no inliers and NaN rms)."""
+    if kind not in REGISTER_KINDS:
+        raise ValueError(f"register must be None or one of {REGISTER_KINDS}, got {kind!r}")
+    G = len(clouds)
+    if G > 256:
+        raise ValueError(f"register= takes at most 256 clouds (groups), got {G}")
+    moving = [i for i in range(G) if i != fixed]
+    reg = dict(R=np.tile(np.eye(3), (G, 1, 1)), t=np.zeros((G, 3)), ok=np.ones(G, dtype=bool), n_iter=0,
+               converged=True, inliers=np.zeros(G, dtype=np.int64), outliers=np.zeros(G, dtype=np.int64),
+               rms_before=np.full(G, np.nan), rms_after=np.full(G, np.nan),
+               transforms=np.tile(np.r_[np.eye(3).ravel(), np.zeros(3)].astype(np.float32), (G, 1)))
+    if not moving:
+        return list(clouds), reg
+    X = np.concatenate([clouds[i] for i in moving]).astype(np.float32)          # boundary cast (SURVEY.md a4)
+    sizes = [clouds[i].shape[0] for i in moving]
+    groups = np.repeat(np.arange(len(moving), dtype=np.uint8), sizes)
+    part, Xr = (align or _gpu_align)(X, np.ascontiguousarray(centers, dtype=np.float32), groups, len(moving), kind,
+                                     max_dist)
+    for key in ("R", "t", "ok", "inliers", "outliers", "rms_before", "rms_after", "transforms"):
+        reg[key][moving] = np.asarray(part[key])
+    reg["n_iter"], reg["converged"] = int(part["n_iter"]), bool(part["converged"])
+    out, at = list(clouds), 0
+    for i, m in zip(moving, sizes):
+        out[i] = np.asarray(Xr[at:at + m], dtype=np.float64)
+        at += m
+    return out, reg
+
+
 def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                 seed: int = 1, fit: Optional[Callable] = None, init: str = "rows", device_clouds=None,
                 export_path=None, describe: bool = False, stats: Optional[Callable] = None,
-                height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None):
+                height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
+                register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
+                align: Optional[Callable] = None):
     """Fuse per-pair (M_i, 3) z,y,x clouds into one K-means reconstruction.
 
     Returns (layers, result) where ``result`` has labels (N,), centers (K, 3),
@@ -231,10 +284,32 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     origin, shape, outside, sizes).  Raises ValueError naming
     ``height_map_cell_log2`` when the words would exceed 4 GiB.  ``grid`` lets tests
     substitute (X, labels, groups, k, G, shape, cell_log2, q) -> (words, outside).
+
+    ``register`` (``"z"``, ``"translation"`` or ``"rigid"``; None: off, every output as
+    without it) first puts the clouds into one frame -- every pair's cloud comes in that
+    pair's own: the model is fitted on cloud ``register_to`` (an index among the non-empty
+    clouds) alone, every other cloud is registered onto its centres (``register_days``,
+    group = cloud, at most 256; ``register_max_dist`` trims, off by default) and
+    transformed; the fuse above then runs unchanged on the registered points, which the
+    fused layer, ``describe`` and ``height_map`` all see.  ``result`` gains
+    ``registration``: R (G, 3, 3), t (G, 3), ok, n_iter, converged, inliers, outliers,
+    rms_before, rms_after, transforms (G, 12) as NumPy arrays (cloud ``register_to``
+    keeps the identity).  ``align`` lets tests substitute
+    (X, centers, groups, G, kind, max_dist) -> (registration dict, registered X).
     """
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to fuse")
+    registration = None
+    if register is not None:
+        if not 0 <= int(register_to) < len(clouds):
+            raise ValueError(f"register_to must index one of the {len(clouds)} non-empty clouds, got {register_to}")
+        ref = int(register_to)
+        ref_dev = None if device_clouds is None else [[c for c in device_clouds if c.numel()][ref]]
+        _, model = kmeans_fuse([clouds[ref]], n_clusters, max_iter, tol, seed=seed, fit=fit, init=init,
+                               device_clouds=ref_dev)
+        clouds, registration = _register_clouds(clouds, model["centers"], ref, register, register_max_dist, align)
+        device_clouds = None       # the registered rows are on the host
     if describe and len(clouds) > 256:
         raise ValueError(f"describe=True takes at most 256 clouds (groups), got {len(clouds)}")
     if height_map and len(clouds) > 256:
@@ -287,6 +362,8 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
                                                  height_map_cell_log2,
                                                  Xfit if (grid is None and Xfit is not X) else X, grid)
         layers += more
+    if registration is not None:
+        result["registration"] = registration
     if export_path is not None:
         export_fused(export_path, X.astype(np.float64), result)
     return layers, result
@@ -308,7 +385,8 @@ def _gpu_assign(X, C: np.ndarray):
 
 
 def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None,
-                  describe: bool = False, stats: Optional[Callable] = None):
+                  describe: bool = False, stats: Optional[Callable] = None, register: Optional[str] = None,
+                  register_max_dist: Optional[float] = None, align: Optional[Callable] = None):
     """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
 
     ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
@@ -326,6 +404,10 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     of the assigned points to their mean, 0 where none), from one exact
     ``cluster_stats`` pass; ``result`` gains ``stats`` = dict(words (1, K, 16), q,
     sizes).  ``stats``: the test stand-in of ``kmeans_fuse``.
+
+    ``register`` (as in ``kmeans_fuse``) first registers every cloud onto the model's
+    centres and labels the registered points: ``dz`` and ``residual`` then measure change,
+    not the frames' offset.  ``result`` gains ``registration``; ``align``: the test stand-in.
     """
     if not isinstance(model, dict):
         model = load_fused(model)
@@ -335,6 +417,10 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to assign")
+    registration = None
+    if register is not None:
+        clouds, registration = _register_clouds(clouds, C, None, register, register_max_dist, align)
+        device_clouds = None       # the registered rows are on the host
     X = np.concatenate(clouds).astype(np.float32)          # boundary cast
     Xq = X
     if device_clouds is not None and assign is None:
@@ -351,6 +437,8 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
          "points"),
     ]
     result = dict(labels=labels, distance=residual, inertia=float(inertia), n_points=X.shape[0])
+    if registration is not None:
+        result["registration"] = registration
     if describe:
         k = C.shape[0]
         st = _describe(X, labels, [X.shape[0]], k, Xq if (stats is None and Xq is not X) else X, stats)
@@ -376,8 +464,15 @@ class HeightMapExtractor(SatellitePlugin):
                  fit: Optional[Callable] = None, init: str = "rows", seed: int = 1, stages=None,
                  export_path=None, _assemble: Optional[Callable] = None, model=None,
                  assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None,
-                 height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None):
+                 height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
+                 register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
+                 align: Optional[Callable] = None):
         self._base = base
+        # register: co-register the run's clouds first (kmeans_fuse / kmeans_assign register=); align: test stand-in
+        self.register = register
+        self.register_to = register_to
+        self.register_max_dist = register_max_dist
+        self._align = align
         # model: a fitted model (kmeans_fuse result, load_fused dict or export_fused path); when given,
         # run fuses nothing and labels the run's clouds against it (kmeans_assign)
         self.model = model
@@ -427,7 +522,9 @@ class HeightMapExtractor(SatellitePlugin):
             use_dev = self._assign is None and all(d is not None for d in dev_clouds)
             assigned, self.last_result = kmeans_assign(host_clouds, self.model, assign=self._assign,
                                                        device_clouds=dev_clouds if use_dev else None,
-                                                       describe=self.describe, stats=self._stats)
+                                                       describe=self.describe, stats=self._stats,
+                                                       register=self.register,
+                                                       register_max_dist=self.register_max_dist, align=self._align)
             return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
@@ -435,7 +532,9 @@ class HeightMapExtractor(SatellitePlugin):
                                               device_clouds=dev_clouds if use_dev else None,
                                               export_path=self.export_path, describe=self.describe,
                                               stats=self._stats, height_map=self.height_map,
-                                              height_map_cell_log2=self.height_map_cell_log2, grid=self._grid)
+                                              height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
+                                              register=self.register, register_to=self.register_to,
+                                              register_max_dist=self.register_max_dist, align=self._align)
         return layers + fused
 
     def _stages_run(self, kml_path, is_debug_mode, is_debug_pair, is_one_random_pair, n) -> List:
@@ -472,13 +571,18 @@ class HeightMapExtractor(SatellitePlugin):
                 return layers
             if self.model is not None:
                 assigned, self.last_result = kmeans_assign(clouds, self.model, assign=self._assign,
-                                                           describe=self.describe, stats=self._stats)
+                                                           describe=self.describe, stats=self._stats,
+                                                           register=self.register,
+                                                           register_max_dist=self.register_max_dist,
+                                                           align=self._align)
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path,
                                                   describe=self.describe, stats=self._stats,
                                                   height_map=self.height_map,
-                                                  height_map_cell_log2=self.height_map_cell_log2, grid=self._grid)
+                                                  height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
+                                                  register=self.register, register_to=self.register_to,
+                                                  register_max_dist=self.register_max_dist, align=self._align)
             return layers + fused
         except Exception as e:   # reference convention: an error layer, never an exception
             import traceback

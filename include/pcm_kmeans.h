@@ -340,6 +340,64 @@ int pcm_height_grid(const float *X, int64_t n,
                     uint64_t *out /* device, n_groups*4*H*W + 2 words, ACCUMULATED: caller zeroes */,
                     void *stream);
 
+/* ---------------------------------------------------------------- registration
+ * Exact statistics for co-registering labelled days (groups) onto fixed centres
+ * (no reference counterpart: the reference builds every pair's cloud in that
+ * pair's own frame and never registers them; DESIGN.md §4 "Registration:
+ * k_align").  X: device float32 n*3 rows (z, y, x); C: device float32 k*3.
+ *
+ * pcm_align_prepare, once per set of centres: copies and checks the centres on
+ * the host (PCM_E_ARG for NaN/Inf; synchronises `stream`), lays the pruning grid
+ * over the box of the CENTRES -- inflated by sqrt(max_d2) when that is finite,
+ * else by an eighth of its longest side, and never by less than 2^-10 of the
+ * centres' reach (coplanar, identical or single centres) -- and builds the exact
+ * candidate lists.  n_hint (the rows a pcm_align_stats call will see) sizes the
+ * grid only.  workspace: caller-owned device memory of pcm_align_workspace(n_hint,
+ * k) bytes, read by every later pcm_align_stats; plan: host, filled here, passed
+ * on unchanged.  info (nullable, host int64[3]): cells, FULL cells, summed
+ * length of the other lists (all 0 without lists: k = 1).
+ *
+ * pcm_align_stats: one launch, no host synchronisation, no allocation.  For
+ * each row i of group g (groups nullable: all group 0), in float32 with every
+ * operation rounded,
+ *   p_a = ((R_a0*x_0 + R_a1*x_1) + R_a2*x_2) + t_a,
+ * T: device float32[n_groups*12], per group R row-major then t (NULL: p = x);
+ * j = the canonical nearest centre of p (the fit's fp32 distance, strict <,
+ * lowest index on ties), d2 that distance; the row is an inlier iff
+ * d2 <= max_d2 (float32 compare; +inf admits every row).  With
+ * pq_a = trunc(ldexp(p_a, q_a)), cq_a = trunc(ldexp(c_ja, q_a)) (q: host
+ * int32[3]) the group's row out + g*PCM_ALIGN_WORDS holds
+ *   word 0        inliers            word 1        outliers (valid rows, trimmed)
+ *   words 2..4    sum pq_a           words 5..7    sum cq_a       (inliers)
+ *   words 8..25   sum pq_a*cq_b, the nine (a, b) row-major, two words each:
+ *                 lo += (uint64)p & 0xffffffff, hi += (uint64)(p >> 32)
+ *   words 26..31  sum pq_a^2 (lo, hi)    words 32..37  sum cq_a^2 (lo, hi)
+ * A row with a non-finite x or p, a group >= n_groups or some
+ * |ldexp(p_a, q_a)| >= 2^25 is skipped: it adds 1 to out[n_groups*38] and
+ * nothing else.  EXACT while fewer than 2^31 rows in all went into one `out`;
+ * every add is an integer add, so the words are the same bits for any row
+ * order, any grid (PCM_ALIGN_BLOCKS overrides it) and any split of the rows over
+ * calls, chunks and ranks.  out: device uint64[n_groups*38 + 1], ACCUMULATED.
+ * PCM_E_ARG when |ldexp(c, q)| >= 2^30 for some centre.  info (nullable, host
+ * int64[3]): cells of the grid, blocks launched, rounds of 64 rows per wave.
+ *
+ * pcm_align_apply writes p (same arithmetic) for every row; a row whose group
+ * is >= n_groups gets NaN. */
+#define PCM_ALIGN_WORDS 38
+#define PCM_ALIGN_MAXG 256
+typedef struct pcm_align_plan {
+    uint64_t opaque[64];
+} pcm_align_plan;
+int pcm_align_workspace(int64_t n_hint, int k, size_t *bytes);
+int pcm_align_prepare(const float *C, int k, int64_t n_hint, float max_d2, void *workspace, size_t workspace_bytes,
+                      pcm_align_plan *plan, int64_t *info, void *stream);
+int pcm_align_stats(const float *X, int64_t n, const uint8_t *groups /* nullable */, int n_groups,
+                    const float *T /* device, nullable */, float max_d2, const int32_t *q /* host int32[3] */,
+                    uint64_t *out /* device, n_groups*38 + 1 words, ACCUMULATED: caller zeroes */,
+                    int64_t *info, const void *workspace, const pcm_align_plan *plan, void *stream);
+int pcm_align_apply(const float *X, int64_t n, const uint8_t *groups /* nullable */, int n_groups,
+                    const float *T /* device */, float *out, void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
