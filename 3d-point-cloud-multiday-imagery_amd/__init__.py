@@ -23,6 +23,8 @@ height_grid(X, shape, cell_log2=, labels=, groups=...) -> HeightGrid: exact per-
 align_stats(X, centers, groups=, transforms=, max_dist=) -> AlignStats: exact per-day sums of the points and their nearest centres
 register_days(X, centers, groups=, kind="rigid")       -> Registration: each day's z offset, translation or rigid motion onto the centres
 apply_registration(X, registration, groups=)           -> the cloud in the centres' frame (the pass's own float32 arithmetic)
+radius_support(X, radius, groups=, max_count=)         -> Support: exact per-row neighbour counts and day support within a radius
+filter_outliers(X, radius, min_neighbors, min_days=)   -> bool keep mask: the radius outlier filter (speckle removal)
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -34,7 +36,7 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
            "SurfaceElements", "height_grid", "HeightGrid", "align_stats", "AlignStats", "register_days", "Registration",
-           "apply_registration"]
+           "apply_registration", "radius_support", "filter_outliers", "Support"]
 
 
 def __getattr__(name):
@@ -57,6 +59,9 @@ def __getattr__(name):
     if name in ("align_stats", "AlignStats", "AlignPlan", "register_days", "Registration", "apply_registration"):
         from . import align
         return getattr(align, name)
+    if name in ("radius_support", "filter_outliers", "Support"):
+        from . import support
+        return getattr(support, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

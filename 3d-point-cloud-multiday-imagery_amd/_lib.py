@@ -18,7 +18,8 @@ SO_PATH = os.environ.get("PCM_SO") or os.path.join(PKG_DIR, "libpcmkm.so")
 UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
     # the Lloyd engine's host units ("Host units"), the slowest to compile first
     "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
-    "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip")]
+    "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip",
+    "pcm_support.hip")]
 
 
 def _deps(path, seen):
@@ -66,6 +67,7 @@ EXPORTS = [
     "pcm_predict_workspace", "pcm_predict", "pcm_dense_predict", "pcm_dense_transform",
     "pcm_cluster_stats", "pcm_height_grid",
     "pcm_align_workspace", "pcm_align_prepare", "pcm_align_stats", "pcm_align_apply",
+    "pcm_support_workspace", "pcm_support_keys", "pcm_support_count",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
@@ -74,6 +76,10 @@ GRID_WORDS = 4           # PCM_GRID_WORDS
 GRID_MAXG = 256          # PCM_GRID_MAXG
 ALIGN_WORDS = 38         # PCM_ALIGN_WORDS
 ALIGN_MAXG = 256         # PCM_ALIGN_MAXG
+SUPPORT_CHUNK = 128      # PCM_SUPPORT_CHUNK: candidate rows staged through LDS at a time
+SUPPORT_TPB = 256        # PCM_SUPPORT_TPB: threads per block of the count kernel
+SUPPORT_MAXG = 64        # PCM_SUPPORT_MAXG
+SUPPORT_INFO_WORDS = 16  # PCM_SUPPORT_INFO_WORDS
 
 
 def stats_words(d: int) -> int:
@@ -221,6 +227,9 @@ def _declare(lib):
         "pcm_align_prepare": ([P, I, I64, ctypes.c_float, P, ctypes.c_size_t, ctypes.POINTER(PcmAlignPlan), P, P], I),
         "pcm_align_stats": ([P, I64, P, I, P, ctypes.c_float, P, P, P, P, ctypes.POINTER(PcmAlignPlan), P], I),
         "pcm_align_apply": ([P, I64, P, I, P, P, P], I),
+        "pcm_support_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_support_keys": ([P, I64, ctypes.c_float, P, P, P], I),
+        "pcm_support_count": ([P, I64, P, I, ctypes.c_float, I, P, P, P, P, P, P, ctypes.c_size_t, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -245,12 +245,77 @@ def _register_clouds(clouds, centers: np.ndarray, fixed: Optional[int], kind: st
     return out, reg
 
 
+def _gpu_support(X: np.ndarray, groups: np.ndarray, n_groups: int, radius: float, min_neighbors: int, min_days: int):
+    """Host (N, 3) float32 rows and their cloud index -> the bool keep mask of ``filter_outliers``
+    (the groups are passed on only when days are asked for)."""
+    import torch
+
+    from .support import filter_outliers
+
+    with _gpu_lock:
+        Xt = torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda()
+        gt = None
+        if min_days > 1:
+            gt = torch.from_numpy(np.ascontiguousarray(groups, dtype=np.uint8)).to(Xt.device)
+        keep = filter_outliers(Xt, radius, min_neighbors, min_days=min_days, groups=gt,
+                               n_groups=n_groups if gt is not None else None)
+        return keep.cpu().numpy()
+
+
+def _denoise_args(denoise, days_allowed: bool):
+    """(radius, min_neighbors[, min_days]) -> (radius, min_neighbors, min_days), checked."""
+    try:
+        parts = tuple(denoise)
+    except TypeError:
+        parts = ()
+    if len(parts) not in (2, 3):
+        raise ValueError(f"denoise must be None, (radius, min_neighbors) or (radius, min_neighbors, min_days), "
+                         f"got {denoise!r}")
+    radius, min_neighbors = float(parts[0]), int(parts[1])
+    min_days = int(parts[2]) if len(parts) == 3 else 1
+    if not (np.isfinite(np.float32(radius)) and np.float32(radius) > 0):
+        raise ValueError(f"denoise radius must be finite and > 0, got {parts[0]!r}")
+    if min_neighbors < 0 or min_neighbors != parts[1]:
+        raise ValueError(f"denoise min_neighbors must be an integer >= 0, got {parts[1]!r}")
+    if min_days < 1 or (len(parts) == 3 and min_days != parts[2]):
+        raise ValueError(f"denoise min_days must be an integer >= 1, got {parts[2]!r}")
+    if min_days > 1 and not days_allowed:
+        raise ValueError("kmeans_assign filters a day by its own counts: denoise takes (radius, min_neighbors) there")
+    return radius, min_neighbors, min_days
+
+
+def _denoise_clouds(clouds, denoise, support: Optional[Callable], by_cloud: bool):
+    """Drop the rows without support from the union of ``clouds`` (group = cloud index when
+    ``by_cloud``, else one group) -> (the clouds with only the kept rows -- a cloud may come out
+    empty --, the ``denoise`` result dict)."""
+    radius, min_neighbors, min_days = _denoise_args(denoise, by_cloud)
+    G = len(clouds) if by_cloud else 1
+    if min_days > 1 and G > 64:
+        raise ValueError(f"denoise with min_days > 1 takes at most 64 clouds (groups), got {G}")
+    sizes = [c.shape[0] for c in clouds]
+    X = np.concatenate(clouds).astype(np.float32)          # boundary cast (SURVEY.md a4)
+    groups = np.repeat(np.arange(len(clouds)), sizes) if by_cloud else np.zeros(X.shape[0], dtype=np.int64)
+    kept = np.asarray((support or _gpu_support)(X, groups, G, radius, min_neighbors, min_days)).astype(bool)
+    if kept.shape != (X.shape[0],):
+        raise ValueError("support must return one bool per row")
+    if not kept.any():
+        raise ValueError(f"denoise removed every point (radius {radius}, min_neighbors {min_neighbors}, "
+                         f"min_days {min_days})")
+    out, removed, at = [], [], 0
+    for c, m in zip(clouds, sizes):
+        k = kept[at:at + m]
+        out.append(c[k])
+        removed.append(int(m - k.sum()))
+        at += m
+    return out, dict(kept=kept, radius=radius, min_neighbors=min_neighbors, min_days=min_days, removed=removed)
+
+
 def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                 seed: int = 1, fit: Optional[Callable] = None, init: str = "rows", device_clouds=None,
                 export_path=None, describe: bool = False, stats: Optional[Callable] = None,
                 height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                 register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
-                align: Optional[Callable] = None):
+                align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None):
     """Fuse per-pair (M_i, 3) z,y,x clouds into one K-means reconstruction.
 
     Returns (layers, result) where ``result`` has labels (N,), centers (K, 3),
@@ -296,10 +361,24 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     rms_before, rms_after, transforms (G, 12) as NumPy arrays (cloud ``register_to``
     keeps the identity).  ``align`` lets tests substitute
     (X, centers, groups, G, kind, max_dist) -> (registration dict, registered X).
+
+    ``denoise`` (``(radius, min_neighbors)`` or ``(radius, min_neighbors, min_days)``; None:
+    off, every output as without it) removes what is not surface, after ``register`` and before
+    the fuse: one ``filter_outliers`` pass over the union of the clouds (group = cloud index)
+    keeps a row with at least ``min_neighbors`` other rows within ``radius`` and, with
+    ``min_days`` > 1 (at most 64 clouds), points of at least that many clouds among itself and
+    them.  Every layer, ``describe`` and ``height_map`` see only the kept rows (a cloud may come
+    out empty).  ``result`` gains ``denoise``: kept (bool over the concatenated input rows),
+    radius, min_neighbors, min_days, removed (per cloud).  ``support`` lets tests substitute
+    (X, groups, G, radius, min_neighbors, min_days) -> mask.
     """
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to fuse")
+    if denoise is not None:
+        # a bad denoise= fails before anything is fitted
+        if _denoise_args(denoise, True)[2] > 1 and len(clouds) > 64:
+            raise ValueError(f"denoise with min_days > 1 takes at most 64 clouds (groups), got {len(clouds)}")
     registration = None
     if register is not None:
         if not 0 <= int(register_to) < len(clouds):
@@ -310,6 +389,10 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
                                device_clouds=ref_dev)
         clouds, registration = _register_clouds(clouds, model["centers"], ref, register, register_max_dist, align)
         device_clouds = None       # the registered rows are on the host
+    denoised = None
+    if denoise is not None:
+        clouds, denoised = _denoise_clouds(clouds, denoise, support, True)
+        device_clouds = None       # the kept rows are on the host
     if describe and len(clouds) > 256:
         raise ValueError(f"describe=True takes at most 256 clouds (groups), got {len(clouds)}")
     if height_map and len(clouds) > 256:
@@ -364,6 +447,8 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
         layers += more
     if registration is not None:
         result["registration"] = registration
+    if denoised is not None:
+        result["denoise"] = denoised
     if export_path is not None:
         export_fused(export_path, X.astype(np.float64), result)
     return layers, result
@@ -386,7 +471,8 @@ def _gpu_assign(X, C: np.ndarray):
 
 def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None,
                   describe: bool = False, stats: Optional[Callable] = None, register: Optional[str] = None,
-                  register_max_dist: Optional[float] = None, align: Optional[Callable] = None):
+                  register_max_dist: Optional[float] = None, align: Optional[Callable] = None, denoise=None,
+                  support: Optional[Callable] = None):
     """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
 
     ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
@@ -408,6 +494,11 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     ``register`` (as in ``kmeans_fuse``) first registers every cloud onto the model's
     centres and labels the registered points: ``dz`` and ``residual`` then measure change,
     not the frames' offset.  ``result`` gains ``registration``; ``align``: the test stand-in.
+
+    ``denoise`` = ``(radius, min_neighbors)`` first drops the rows of the (registered) clouds
+    with fewer than ``min_neighbors`` other rows within ``radius`` -- the later day is filtered
+    by its own counts, as one group; a ``min_days`` above 1 raises ValueError -- and labels the
+    rest.  ``result`` gains ``denoise`` as in ``kmeans_fuse``; ``support``: the test stand-in.
     """
     if not isinstance(model, dict):
         model = load_fused(model)
@@ -417,10 +508,16 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to assign")
+    if denoise is not None:
+        _denoise_args(denoise, False)
     registration = None
     if register is not None:
         clouds, registration = _register_clouds(clouds, C, None, register, register_max_dist, align)
         device_clouds = None       # the registered rows are on the host
+    denoised = None
+    if denoise is not None:
+        clouds, denoised = _denoise_clouds(clouds, denoise, support, False)
+        device_clouds = None       # the kept rows are on the host
     X = np.concatenate(clouds).astype(np.float32)          # boundary cast
     Xq = X
     if device_clouds is not None and assign is None:
@@ -439,6 +536,8 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     result = dict(labels=labels, distance=residual, inertia=float(inertia), n_points=X.shape[0])
     if registration is not None:
         result["registration"] = registration
+    if denoised is not None:
+        result["denoise"] = denoised
     if describe:
         k = C.shape[0]
         st = _describe(X, labels, [X.shape[0]], k, Xq if (stats is None and Xq is not X) else X, stats)
@@ -466,8 +565,11 @@ class HeightMapExtractor(SatellitePlugin):
                  assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None,
                  height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                  register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
-                 align: Optional[Callable] = None):
+                 align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None):
         self._base = base
+        # denoise: drop the rows without support first (kmeans_fuse / kmeans_assign denoise=); support: test stand-in
+        self.denoise = denoise
+        self._support = support
         # register: co-register the run's clouds first (kmeans_fuse / kmeans_assign register=); align: test stand-in
         self.register = register
         self.register_to = register_to
@@ -524,7 +626,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                        device_clouds=dev_clouds if use_dev else None,
                                                        describe=self.describe, stats=self._stats,
                                                        register=self.register,
-                                                       register_max_dist=self.register_max_dist, align=self._align)
+                                                       register_max_dist=self.register_max_dist, align=self._align,
+                                              denoise=self.denoise, support=self._support)
             return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
@@ -534,7 +637,8 @@ class HeightMapExtractor(SatellitePlugin):
                                               stats=self._stats, height_map=self.height_map,
                                               height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
                                               register=self.register, register_to=self.register_to,
-                                              register_max_dist=self.register_max_dist, align=self._align)
+                                              register_max_dist=self.register_max_dist, align=self._align,
+                                              denoise=self.denoise, support=self._support)
         return layers + fused
 
     def _stages_run(self, kml_path, is_debug_mode, is_debug_pair, is_one_random_pair, n) -> List:
@@ -574,7 +678,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                            describe=self.describe, stats=self._stats,
                                                            register=self.register,
                                                            register_max_dist=self.register_max_dist,
-                                                           align=self._align)
+                                                           align=self._align, denoise=self.denoise,
+                                                           support=self._support)
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path,
@@ -582,7 +687,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                   height_map=self.height_map,
                                                   height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
                                                   register=self.register, register_to=self.register_to,
-                                                  register_max_dist=self.register_max_dist, align=self._align)
+                                                  register_max_dist=self.register_max_dist, align=self._align,
+                                              denoise=self.denoise, support=self._support)
             return layers + fused
         except Exception as e:   # reference convention: an error layer, never an exception
             import traceback

@@ -398,6 +398,58 @@ int pcm_align_stats(const float *X, int64_t n, const uint8_t *groups /* nullable
 int pcm_align_apply(const float *X, int64_t n, const uint8_t *groups /* nullable */, int n_groups,
                     const float *T /* device */, float *out, void *stream);
 
+/* ---------------------------------------------------------------- support
+ * Exact fixed-radius neighbour counts and day support of a cloud, the basis of
+ * the radius outlier filter (no reference counterpart: the reference never
+ * removes the speckle of its disparity maps; DESIGN.md §4 "Support").
+ * X: device float32 n*3 rows (z, y, x).  With r2 = radius * radius (float32),
+ * row j is a neighbour of row i (j != i) iff, in float32, every operation
+ * rounded, no contraction,
+ *   dz = z_i - z_j, dy = y_i - y_j, dx = x_i - x_j,  (dz*dz + dy*dy) + dx*dx <= r2.
+ * Duplicates of a row are its neighbours; a row with a NaN or Inf coordinate
+ * has no neighbours, is nobody's neighbour and gets counts = days = 0.
+ *   counts[i] = min(neighbours of i, max_count)      (max_count < 0: no limit)
+ *   days[i]   = distinct groups among row i and its neighbours (exact whatever
+ *               max_count is; groups NULL: every row in group 0)
+ * Three steps, all stream-ordered, no host synchronisation, no allocation:
+ *   pcm_support_keys   fills info (device int64[PCM_SUPPORT_INFO_WORDS]) and
+ *                      keys (device int64[n]): the row's cell, 21 bits per axis,
+ *                      x fastest; 2^63 - 1 for a non-finite row;
+ *   (the caller sorts: sorted_keys ascending and perm, sorted_keys[i] =
+ *    keys[perm[i]] -- any sort, ties in any order)
+ *   pcm_support_count  gathers the cell-sorted copy into the workspace
+ *                      (pcm_support_workspace bytes) and counts; writes counts
+ *                      (device int32[n]) and, when days is not NULL, days
+ *                      (device int32[n]) in the caller's row order.
+ * info: [0] the cell exponent s (a cell is 2^s units on a side: the smallest s
+ * with 2^s >= radius (1 + 2^-20), at least -32, raised until |x| 2^-s <= 2^40
+ * and every axis spans at most 2^21 cells); [1..3] the cell of the box's low
+ * corner (z, y, x); [4..6] the bits each axis needs; [7] the rows skipped as
+ * non-finite; [8..14] internal; [15] set when perm held a value outside [0, n)
+ * (that row is left unwritten).  groups: device uint8[n] with values below
+ * n_groups (the caller checks; the kernel uses the low 6 bits).
+ * The results are integers decided by the predicate alone -- the cells only
+ * prune -- so they are the same bits for any row order, sort and launch shape.
+ * Cost: a row is tested against every row of the cells around it, so the count
+ * grows with the SQUARE of a cell's population (many duplicates, or a radius
+ * far above the point spacing).  A cell run longer than PCM_SUPPORT_CHUNK rows
+ * is staged in several chunks.  PCM_SUPPORT_PHASE=1 / 2 in the environment runs
+ * only the gather / only the count (measurement).
+ * The arguments are checked before any device call (PCM_E_ARG: n < 0,
+ * n >= 2^31, radius not finite or <= 0, n_groups outside 1..PCM_SUPPORT_MAXG,
+ * a null pointer with n > 0, a workspace too small); n = 0 succeeds without
+ * counting. */
+#define PCM_SUPPORT_CHUNK 128
+#define PCM_SUPPORT_TPB 256
+#define PCM_SUPPORT_MAXG 64
+#define PCM_SUPPORT_INFO_WORDS 16
+int pcm_support_workspace(int64_t n, size_t *bytes);
+int pcm_support_keys(const float *X, int64_t n, float radius, int64_t *keys, int64_t *info, void *stream);
+int pcm_support_count(const float *X, int64_t n, const uint8_t *groups /* nullable */, int n_groups, float radius,
+                      int max_count, const int64_t *sorted_keys, const int64_t *perm, int32_t *counts,
+                      int32_t *days /* nullable */, int64_t *info, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
