@@ -25,6 +25,8 @@ register_days(X, centers, groups=, kind="rigid")       -> Registration: each day
 apply_registration(X, registration, groups=)           -> the cloud in the centres' frame (the pass's own float32 arithmetic)
 radius_support(X, radius, groups=, max_count=)         -> Support: exact per-row neighbour counts and day support within a radius
 filter_outliers(X, radius, min_neighbors, min_days=)   -> bool keep mask: the radius outlier filter (speckle removal)
+voxel_grid(X, voxel, origin=, groups=, q=)             -> Voxels: exact per-voxel count, centroid sums, lowest row and day mask
+voxel_downsample(X, voxel, mode=, min_count=, min_days=) -> Downsampled: one point per occupied voxel (thinning, persistence filter)
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -36,7 +38,8 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "photoconsistency_map", "left_right_consistency", "lloyd_predict", "LloydPrediction", "dense_predict",
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
            "SurfaceElements", "height_grid", "HeightGrid", "align_stats", "AlignStats", "register_days", "Registration",
-           "apply_registration", "radius_support", "filter_outliers", "Support"]
+           "apply_registration", "radius_support", "filter_outliers", "Support", "voxel_grid",
+           "voxel_downsample", "Voxels", "Downsampled"]
 
 
 def __getattr__(name):
@@ -62,6 +65,9 @@ def __getattr__(name):
     if name in ("radius_support", "filter_outliers", "Support"):
         from . import support
         return getattr(support, name)
+    if name in ("voxel_grid", "voxel_downsample", "Voxels", "Downsampled"):
+        from . import voxel
+        return getattr(voxel, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

@@ -19,7 +19,7 @@ UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
     # the Lloyd engine's host units ("Host units"), the slowest to compile first
     "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
     "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip",
-    "pcm_support.hip")]
+    "pcm_support.hip", "pcm_voxel.hip")]
 
 
 def _deps(path, seen):
@@ -68,6 +68,7 @@ EXPORTS = [
     "pcm_cluster_stats", "pcm_height_grid",
     "pcm_align_workspace", "pcm_align_prepare", "pcm_align_stats", "pcm_align_apply",
     "pcm_support_workspace", "pcm_support_keys", "pcm_support_count",
+    "pcm_voxel_workspace", "pcm_voxel_keys", "pcm_voxel_count", "pcm_voxel_reduce",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
@@ -80,6 +81,12 @@ SUPPORT_CHUNK = 128      # PCM_SUPPORT_CHUNK: candidate rows staged through LDS 
 SUPPORT_TPB = 256        # PCM_SUPPORT_TPB: threads per block of the count kernel
 SUPPORT_MAXG = 64        # PCM_SUPPORT_MAXG
 SUPPORT_INFO_WORDS = 16  # PCM_SUPPORT_INFO_WORDS
+VOXEL_TPB = 256          # PCM_VOXEL_TPB: threads per block of the key, head and reduce kernels
+VOXEL_MAXG = 64          # PCM_VOXEL_MAXG
+VOXEL_INFO_WORDS = 16    # PCM_VOXEL_INFO_WORDS
+VOXEL_E_NONFINITE = 1    # PCM_VOXEL_E_NONFINITE: a cell of the box is not finite
+VOXEL_E_MAGNITUDE = 2    # PCM_VOXEL_E_MAGNITUDE: |cell| > 2^40
+VOXEL_E_SPAN = 4         # PCM_VOXEL_E_SPAN: an axis spans more than 2^21 cells
 
 
 def stats_words(d: int) -> int:
@@ -230,6 +237,10 @@ def _declare(lib):
         "pcm_support_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
         "pcm_support_keys": ([P, I64, ctypes.c_float, P, P, P], I),
         "pcm_support_count": ([P, I64, P, I, ctypes.c_float, I, P, P, P, P, P, P, ctypes.c_size_t, P], I),
+        "pcm_voxel_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_voxel_keys": ([P, I64, P, P, P, P, P], I),
+        "pcm_voxel_count": ([P, I64, P, P, ctypes.c_size_t, P], I),
+        "pcm_voxel_reduce": ([P, I64, P, I, P, P, P, I64, P, P, P, P, P, P, P, P, ctypes.c_size_t, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

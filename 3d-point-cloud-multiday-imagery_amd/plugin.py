@@ -310,12 +310,61 @@ def _denoise_clouds(clouds, denoise, support: Optional[Callable], by_cloud: bool
     return out, dict(kept=kept, radius=radius, min_neighbors=min_neighbors, min_days=min_days, removed=removed)
 
 
+def _gpu_voxels(X: np.ndarray, size):
+    """Host (n, 3) float32 rows -> (centroid per occupied voxel float32 (M, 3), counts (M,), inverse (n,)):
+    ``voxel_downsample`` in centroid mode on the origin-0 lattice."""
+    import torch
+
+    from .voxel import voxel_downsample
+
+    with _gpu_lock:
+        ds = voxel_downsample(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda(), size)
+        return ds.points.cpu().numpy(), ds.voxels.counts.cpu().numpy(), ds.voxels.inverse.cpu().numpy()
+
+
+def _voxel_args(voxel):
+    """A size or (vz, vy, vx) -> three positive finite float32 sizes as floats, checked."""
+    try:
+        with np.errstate(over="ignore"):
+            v = np.asarray(voxel, dtype=np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        v = np.zeros(0, dtype=np.float32)
+    if v.shape == ():
+        v = np.full(3, v, dtype=np.float32)
+    if v.shape != (3,) or not (np.isfinite(v).all() and (v > 0).all()):
+        raise ValueError(f"voxel must be None, a size or (vz, vy, vx), finite and > 0 in float32, got {voxel!r}")
+    return tuple(float(t) for t in v)
+
+
+def _thin_clouds(clouds, size, voxels: Optional[Callable]):
+    """Thin every cloud separately on the common origin-0 lattice (centroid mode) -> (the thinned
+    clouds -- they stay distinguishable --, the ``voxel`` result dict)."""
+    out, kept_rows, counts, inverse, at = [], [], [], [], 0
+    for c in clouds:
+        n = c.shape[0]
+        pts, cnt, inv = (np.zeros((0, 3), np.float32), np.zeros(0, np.int32), np.zeros(0, np.int32)) if not n else \
+            (voxels or _gpu_voxels)(c.astype(np.float32), size)       # boundary cast (SURVEY.md a4)
+        pts, cnt, inv = np.asarray(pts), np.asarray(cnt), np.asarray(inv).astype(np.int64)
+        m = pts.shape[0]
+        if pts.shape != (m, 3) or cnt.shape != (m,) or inv.shape != (n,) or (n and not -1 <= inv.min() <= inv.max() < m):
+            raise ValueError("voxels must return (points (M, 3), counts (M,), inverse (n,) in [-1, M))")
+        out.append(pts.astype(np.float64))
+        kept_rows.append(int(m))
+        counts.append(cnt.astype(np.int32))
+        inverse.append(np.where(inv >= 0, inv + at, -1))
+        at += m
+    if not at:
+        raise ValueError(f"voxel thinning left no point (voxel {size})")
+    return out, dict(size=size, kept_rows=kept_rows, counts=np.concatenate(counts), inverse=np.concatenate(inverse))
+
+
 def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: int = 300, tol: float = 1e-4,
                 seed: int = 1, fit: Optional[Callable] = None, init: str = "rows", device_clouds=None,
                 export_path=None, describe: bool = False, stats: Optional[Callable] = None,
                 height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                 register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
-                align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None):
+                align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None, voxel=None,
+                voxels: Optional[Callable] = None):
     """Fuse per-pair (M_i, 3) z,y,x clouds into one K-means reconstruction.
 
     Returns (layers, result) where ``result`` has labels (N,), centers (K, 3),
@@ -371,10 +420,21 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     out empty).  ``result`` gains ``denoise``: kept (bool over the concatenated input rows),
     radius, min_neighbors, min_days, removed (per cloud).  ``support`` lets tests substitute
     (X, groups, G, radius, min_neighbors, min_days) -> mask.
+
+    ``voxel`` (a size or ``(vz, vy, vx)``; None: off, every output as without it) thins the clouds
+    after ``register`` and ``denoise`` and before the fit: every cloud SEPARATELY is reduced to the
+    exact centroids of its occupied voxels (``voxel_downsample``, centroid mode) on the common
+    lattice anchored at the origin, so the fit weighs surface, not sampling density, and the clouds
+    stay distinguishable: every layer, ``describe``, ``height_map`` and their ``sizes`` see the
+    thinned rows.  ``result`` gains ``voxel``: size (vz, vy, vx), kept_rows (per cloud), counts
+    (rows per kept voxel, concatenated) and inverse (over the concatenated rows that entered the
+    thinning: the thinned row of each, -1 for a NaN or Inf row), so ``labels[inverse]`` labels the
+    original points.  ``voxels`` lets tests substitute (X, (vz, vy, vx)) -> (points, counts, inverse).
     """
     clouds = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in clouds if np.asarray(c).size]
     if not clouds:
         raise ValueError("no point cloud layers to fuse")
+    voxel_size = None if voxel is None else _voxel_args(voxel)     # a bad voxel= fails before anything is fitted
     if denoise is not None:
         # a bad denoise= fails before anything is fitted
         if _denoise_args(denoise, True)[2] > 1 and len(clouds) > 64:
@@ -393,6 +453,10 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
     if denoise is not None:
         clouds, denoised = _denoise_clouds(clouds, denoise, support, True)
         device_clouds = None       # the kept rows are on the host
+    thinned = None
+    if voxel_size is not None:
+        clouds, thinned = _thin_clouds(clouds, voxel_size, voxels)
+        device_clouds = None       # the centroids are on the host
     if describe and len(clouds) > 256:
         raise ValueError(f"describe=True takes at most 256 clouds (groups), got {len(clouds)}")
     if height_map and len(clouds) > 256:
@@ -449,6 +513,8 @@ def kmeans_fuse(clouds: Sequence[np.ndarray], n_clusters: int = 1024, max_iter: 
         result["registration"] = registration
     if denoised is not None:
         result["denoise"] = denoised
+    if thinned is not None:
+        result["voxel"] = thinned
     if export_path is not None:
         export_fused(export_path, X.astype(np.float64), result)
     return layers, result
@@ -565,8 +631,12 @@ class HeightMapExtractor(SatellitePlugin):
                  assign: Optional[Callable] = None, describe: bool = False, stats: Optional[Callable] = None,
                  height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                  register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
-                 align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None):
+                 align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None, voxel=None,
+                 voxels: Optional[Callable] = None):
         self._base = base
+        # voxel: thin every cloud onto a lattice before the fit (kmeans_fuse voxel=); voxels: test stand-in
+        self.voxel = voxel
+        self._voxels = voxels
         # denoise: drop the rows without support first (kmeans_fuse / kmeans_assign denoise=); support: test stand-in
         self.denoise = denoise
         self._support = support
@@ -638,7 +708,8 @@ class HeightMapExtractor(SatellitePlugin):
                                               height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
                                               register=self.register, register_to=self.register_to,
                                               register_max_dist=self.register_max_dist, align=self._align,
-                                              denoise=self.denoise, support=self._support)
+                                              denoise=self.denoise, support=self._support, voxel=self.voxel,
+                                              voxels=self._voxels)
         return layers + fused
 
     def _stages_run(self, kml_path, is_debug_mode, is_debug_pair, is_one_random_pair, n) -> List:
@@ -688,7 +759,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                   height_map_cell_log2=self.height_map_cell_log2, grid=self._grid,
                                                   register=self.register, register_to=self.register_to,
                                                   register_max_dist=self.register_max_dist, align=self._align,
-                                              denoise=self.denoise, support=self._support)
+                                                  denoise=self.denoise, support=self._support, voxel=self.voxel,
+                                                  voxels=self._voxels)
             return layers + fused
         except Exception as e:   # reference convention: an error layer, never an exception
             import traceback

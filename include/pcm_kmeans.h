@@ -450,6 +450,66 @@ int pcm_support_count(const float *X, int64_t n, const uint8_t *groups /* nullab
                       int32_t *days /* nullable */, int64_t *info, void *workspace, size_t workspace_bytes,
                       void *stream);
 
+/* ---------------------------------------------------------------- voxels
+ * Exact voxel-grid reduction of a cloud: one entry per occupied voxel with its
+ * count, fixed-point coordinate sums, lowest row and the groups (days) that saw
+ * it (no reference counterpart; DESIGN.md §4 "Voxels").  X: device float32 n*3
+ * rows (z, y, x).  voxel, origin: HOST float32[3] (z, y, x): sizes finite and
+ * > 0, origin finite.  On axis a the cell of a finite row is, in float32, every
+ * operation rounded, no contraction,
+ *   c_a = floorf((x_a - origin_a) * inv_a),  inv_a = (float)(1.0 / (double)voxel_a)
+ * (inv_a must be a finite normal float32).  A row with a NaN or Inf coordinate
+ * belongs to no voxel.  Four steps, all stream-ordered, no allocation:
+ *   pcm_voxel_keys    fills info (device int64[PCM_VOXEL_INFO_WORDS]) and keys
+ *                     (device int64[n]): the row's cell relative to the cell of
+ *                     the box's low corner, 21 bits per axis, x fastest; 2^63 - 1
+ *                     for a non-finite row (and for every row when info[0] != 0);
+ *   (the caller sorts: sorted_keys ascending and perm, sorted_keys[i] =
+ *    keys[perm[i]] -- any sort, ties in any order)
+ *   pcm_voxel_count   counts the segment heads of the sorted keys per wave of 64
+ *                     rows into the workspace (pcm_voxel_workspace bytes), scans
+ *                     them and writes the number of voxels M to info[8];
+ *   (the caller reads info once: the error word, M, the skipped rows, the box)
+ *   pcm_voxel_reduce  with m = M: for voxel v in ascending (cz, cy, cx) order
+ *                     cells[v*3 + a] (int64) the absolute cell, counts[v] (int32),
+ *                     sums[v*3 + a] (int64) = sum of trunc(ldexp(x_a, q_a)) taken
+ *                     as int32 (q: HOST int32[3]), first[v] (int32) the lowest
+ *                     row, day_mask[v] (int64, with groups) bit g set iff a row of
+ *                     group g is in v; inverse[i] (int32[n]) the voxel of row i,
+ *                     -1 for a non-finite row.  It initialises the outputs itself.
+ * info: [0] 0 or PCM_VOXEL_E_* bits over the finite rows' box: a non-finite
+ * cell, |cell| > 2^40, an axis spanning more than 2^21 cells (or all three
+ * spanning exactly 2^21: the last key would be the skip key); [1..3] the cell of
+ * the box's low corner; [4..6] the cells each axis spans; [7] the rows skipped
+ * as non-finite; [8] M; [9..14] the box of the finite rows, low then high corner,
+ * as order-preserving uint32 (u = bits ^ 0xffffffff for a negative float, bits |
+ * 0x80000000 otherwise); [15] set when perm held a value outside [0, n) or the
+ * keys changed between count and reduce (such rows are left unwritten).
+ * groups: device uint8[n] with values below n_groups (the caller checks; the
+ * kernel uses the low 6 bits).  Only a wave's first and last segment, when they
+ * continue in a neighbouring wave, are written with integer atomics; integer
+ * adds, ors and minima commute, so the outputs are the same bits for any row
+ * order, sort and launch shape.  Exact while |ldexp(x_a, q_a)| < 2^31.
+ * The arguments are checked before any device call (PCM_E_ARG: n < 0,
+ * n >= 2^31, a null pointer, a bad size or origin, m outside [0, n], n_groups
+ * outside 1..PCM_VOXEL_MAXG, a workspace too small); n = 0 makes no device call
+ * beyond initialising info. */
+#define PCM_VOXEL_TPB 256
+#define PCM_VOXEL_MAXG 64
+#define PCM_VOXEL_INFO_WORDS 16
+#define PCM_VOXEL_E_NONFINITE 1
+#define PCM_VOXEL_E_MAGNITUDE 2
+#define PCM_VOXEL_E_SPAN 4
+int pcm_voxel_workspace(int64_t n, size_t *bytes);
+int pcm_voxel_keys(const float *X, int64_t n, const float *voxel /* host float[3] */,
+                   const float *origin /* host float[3] */, int64_t *keys, int64_t *info, void *stream);
+int pcm_voxel_count(const int64_t *sorted_keys, int64_t n, int64_t *info, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int pcm_voxel_reduce(const float *X, int64_t n, const uint8_t *groups /* nullable */, int n_groups,
+                     const int32_t *q /* host int32[3] */, const int64_t *sorted_keys, const int64_t *perm, int64_t m,
+                     int64_t *cells, int32_t *counts, int64_t *sums, int32_t *first, int64_t *day_mask /* nullable */,
+                     int32_t *inverse, int64_t *info, const void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
