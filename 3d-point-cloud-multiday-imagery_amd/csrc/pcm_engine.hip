@@ -833,6 +833,57 @@ int pcm_debug_layout(pcm_engine *e, void *xs_out, int32_t *lab_out, uint32_t *pe
     });
 }
 
+// Debug (not in the public header): the integers of the built layout, out[0 .. 20):
+// sub, zlev, tile_cap, npad, ntiles, ntiles_cap, the sort plan's bits, npass, wb, nblk, nseg,
+// has_dmap, use_xz, tiles_lpt, bytes per sorted-order label, ncells, n, d, prune, k.
+// Reads host state only.
+int pcm_debug_layout_facts(pcm_engine *e, int64_t *out, int cap) {
+    if (!e || !out || cap < 20) return fail(PCM_E_ARG, "bad argument");
+    if (!e->layout_ready) return fail(PCM_E_STATE, "layout not built");
+    const int64_t f[20] = {e->sub, e->zlev, (int64_t)e->tile_cap, e->npad, e->ntiles, e->ntiles_cap, e->rs_bits,
+                           e->rs_npass, e->rs_wb, e->rs_nblk, e->rs_nseg, e->has_dmap, e->use_xz, e->tiles_lpt,
+                           (int64_t)lsize(e), e->g.ncells, e->n, e->d, e->g.prune, e->k};
+    std::copy(f, f + 20, out);
+    return 0;
+}
+
+// Debug (not in the public header): one named buffer of the built layout copied to the caller's
+// device buffer `out` of exactly `bytes` bytes; *need (optional) = the buffer's size, also when the
+// copy is refused for its size (out null: the size query alone).  A buffer the layout does not have
+// (no compressed stream, no position maps, ...) is PCM_E_STATE.  Copies only: the engine's state
+// and its scratch stay as they are.
+int pcm_debug_layout_buffer(pcm_engine *e, const char *name, void *out, size_t bytes, size_t *need, void *stream) {
+    if (!e || !name) return fail(PCM_E_ARG, "bad argument");
+    if (!e->layout_ready) return fail(PCM_E_STATE, "layout not built");
+    const std::string nm(name);
+    const size_t nc = (size_t)e->g.ncells, n = (size_t)e->n, nt = (size_t)std::max(0LL, e->ntiles);
+    const bool pts = n > 0;
+    const void *src = nullptr;
+    size_t sz = 0;
+    bool known = true, have = true;
+    if (nm == "cell_start") { src = e->cell_start; sz = (nc + 1) * 4; }
+    else if (nm == "tile_off") { src = e->tile_off; sz = (nc + 1) * 4; }
+    else if (nm == "fc_cnt") { src = e->fc_cnt; sz = nc * 4; }
+    else if (nm == "sub_start") { src = e->sub_start; sz = ((nc << (e->sub ? e->d : 0)) + 1) * 4; have = pts && e->zlev == 0; }
+    else if (nm == "tiles") { src = e->tiles; sz = nt * sizeof(uint4); have = pts; }
+    else if (nm == "tsum") { src = e->tsum; sz = nt * e->d * sizeof(long long); have = pts; }
+    else if (nm == "tmeta") { src = e->tmeta; sz = nt * sizeof(uint4); have = pts && e->use_xz; }
+    else if (nm == "xz") { src = e->xz; sz = align_up((size_t)e->npad) * 8; have = pts && e->use_xz; }
+    else if (nm == "zpts") { src = e->zpts; sz = 32 * 16 * sizeof(unsigned long long); have = pts; }
+    else if (nm == "tbox") { src = e->tbox; sz = nt * 2 * sizeof(float4); have = pts && e->zlev > 0; }
+    else if (nm == "dmap") { src = e->dmap; sz = 2 * n * 4; have = pts && e->has_dmap; }
+    else if (nm == "torig") { src = e->torig; sz = nt * 4; have = pts && e->tiles_lpt; }
+    else if (nm == "tpos") { src = e->tpos; sz = nt * 4; have = pts && e->tiles_lpt; }
+    else known = false;
+    if (!known) return fail(PCM_E_ARG, "pcm_debug_layout_buffer: unknown buffer " + nm);
+    if (!have) return fail(PCM_E_STATE, "pcm_debug_layout_buffer: this layout has no " + nm);
+    if (need) *need = sz;
+    if (!out) return 0;
+    if (bytes != sz) return fail(PCM_E_ARG, "pcm_debug_layout_buffer: " + nm + " holds " + std::to_string(sz) + " bytes");
+    if (sz) HIPCHK(hipMemcpyAsync(out, src, sz, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
 #ifdef PCM_DBG_TIMING
 // This unit's copies of the stamp arrays (pcm_debug.hpp): the list and update kernels' and k_lloyd1's.
 int pcm_debug_timing(unsigned long long *out, int nblocks) {

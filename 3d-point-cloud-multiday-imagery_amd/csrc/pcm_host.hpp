@@ -90,6 +90,8 @@ struct pcm_engine {
     int zlev = 0;                    // crowded layouts (tight clusters): Morton levels of the in-cell order and the tile lists
     bool has_dmap = false;           // the current layout kept its sort's position maps (2-pass sorts)
     int sub = 0;                     // the current layout is sorted by sub-cell
+    int rs_bits = 0, rs_npass = 0, rs_wb = 0;   // the current layout's sort plan (RsPlan), kept for
+    long long rs_nblk = 0, rs_nseg = 0;         // pcm_debug_layout_facts only
     int num_cu = 256;
     double drift_alpha = 2.0, drift_kappa = 0.05;  // candidate-list reuse policy (see k_upd)
     int iscale = 0;                  // exact-inertia weight exponent (from the global q)

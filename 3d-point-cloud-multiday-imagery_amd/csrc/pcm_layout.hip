@@ -296,6 +296,19 @@ int pcm::host_bbox(const void *X, int dtype, int d, long long n, float *part, un
 
 extern "C" {
 
+// Debug (not in the public header): make_grid alone, for the tests' restatement of it.  Host
+// arithmetic only, no HIP call: it runs on a machine without a GPU.
+int pcm_debug_make_grid(int d, const double *lo, const double *hi, double target, int *G, int64_t *ncells,
+                        int *prune) {
+    if (d < 1 || d > MAXD || !lo || !hi || !G || !ncells || !prune) return fail(PCM_E_ARG, "bad argument");
+    Grid g;
+    make_grid(g, d, lo, hi, target);
+    for (int a = 0; a < MAXD; ++a) G[a] = g.G[a];
+    *ncells = g.ncells;
+    *prune = g.prune;
+    return 0;
+}
+
 int pcm_layout_bbox(pcm_engine *e, const void *X, int64_t n, void *stream, double *lo, double *hi, double *maxabs) {
     if (!e || (!X && n > 0) || n < 0 || !lo || !hi || !maxabs) return fail(PCM_E_ARG, "bad argument");
     if (n >= (1LL << 32) - 8) return fail(PCM_E_ARG, "n must be < 2^32 per engine");
@@ -446,6 +459,8 @@ int pcm_layout_build(pcm_engine *e, const void *X, const int32_t *q, int64_t gid
     // every cell holds ceil(count / cap) <= count / cap + 1 tiles
     e->ntiles_cap = nc + n / e->tile_cap + 1;
     e->ntiles = -1;
+    e->rs_bits = e->rs_npass = e->rs_wb = 0;   // no sort yet (an empty cloud has none)
+    e->rs_nblk = e->rs_nseg = 0;
 
     // persistent layout buffers (no allocation when an earlier layout was as large)
     HIPCHK(e->xs.ensure((size_t)e->d * e->npad * ts));
@@ -497,6 +512,11 @@ int pcm_layout_build(pcm_engine *e, const void *X, const int32_t *q, int64_t gid
         return fail(PCM_E_HIP, "layout: rocprim size query failed");
     RsPlan p;
     if (int rc = rs_plan(e->dtype, e->d, n, bits, p)) return rc;
+    e->rs_bits = (int)bits;
+    e->rs_npass = p.npass;
+    e->rs_wb = p.wb;
+    e->rs_nblk = p.nblk;
+    e->rs_nseg = p.nseg;
     const size_t o_tcnt = align_up(p.total), o_tmp = align_up(o_tcnt + nc * 4), ws_need = o_tmp + scan_bytes;
     if (e->ws.ensure(ws_need) != hipSuccess) return fail(PCM_E_NOMEM, "layout scratch");
     char *wb = (char *)e->ws;
