@@ -27,6 +27,7 @@ radius_support(X, radius, groups=, max_count=)         -> Support: exact per-row
 filter_outliers(X, radius, min_neighbors, min_days=)   -> bool keep mask: the radius outlier filter (speckle removal)
 voxel_grid(X, voxel, origin=, groups=, q=)             -> Voxels: exact per-voxel count, centroid sums, lowest row and day mask
 voxel_downsample(X, voxel, mode=, min_count=, min_days=) -> Downsampled: one point per occupied voxel (thinning, persistence filter)
+nearest_points(X, Y, max_dist, groups=, target_groups=) -> Nearest: exact nearest row of another cloud within a radius, its squared distance
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -39,7 +40,7 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
            "SurfaceElements", "height_grid", "HeightGrid", "align_stats", "AlignStats", "register_days", "Registration",
            "apply_registration", "radius_support", "filter_outliers", "Support", "voxel_grid",
-           "voxel_downsample", "Voxels", "Downsampled"]
+           "voxel_downsample", "Voxels", "Downsampled", "nearest_points", "Nearest"]
 
 
 def __getattr__(name):
@@ -68,6 +69,9 @@ def __getattr__(name):
     if name in ("voxel_grid", "voxel_downsample", "Voxels", "Downsampled"):
         from . import voxel
         return getattr(voxel, name)
+    if name in ("nearest_points", "Nearest"):
+        from . import nearest
+        return getattr(nearest, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

@@ -19,7 +19,7 @@ UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
     # the Lloyd engine's host units ("Host units"), the slowest to compile first
     "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
     "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip",
-    "pcm_support.hip", "pcm_voxel.hip")]
+    "pcm_support.hip", "pcm_voxel.hip", "pcm_nearest.hip")]
 
 
 def _deps(path, seen):
@@ -69,6 +69,7 @@ EXPORTS = [
     "pcm_align_workspace", "pcm_align_prepare", "pcm_align_stats", "pcm_align_apply",
     "pcm_support_workspace", "pcm_support_keys", "pcm_support_count",
     "pcm_voxel_workspace", "pcm_voxel_keys", "pcm_voxel_count", "pcm_voxel_reduce",
+    "pcm_nearest_workspace", "pcm_nearest_keys", "pcm_nearest_find",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
@@ -87,6 +88,9 @@ VOXEL_INFO_WORDS = 16    # PCM_VOXEL_INFO_WORDS
 VOXEL_E_NONFINITE = 1    # PCM_VOXEL_E_NONFINITE: a cell of the box is not finite
 VOXEL_E_MAGNITUDE = 2    # PCM_VOXEL_E_MAGNITUDE: |cell| > 2^40
 VOXEL_E_SPAN = 4         # PCM_VOXEL_E_SPAN: an axis spans more than 2^21 cells
+NEAREST_CHUNK = 128      # PCM_NEAREST_CHUNK: target rows staged through LDS at a time
+NEAREST_TPB = 256        # PCM_NEAREST_TPB: threads per block of the scan kernel
+NEAREST_INFO_WORDS = 20  # PCM_NEAREST_INFO_WORDS
 
 
 def stats_words(d: int) -> int:
@@ -241,6 +245,9 @@ def _declare(lib):
         "pcm_voxel_keys": ([P, I64, P, P, P, P, P], I),
         "pcm_voxel_count": ([P, I64, P, P, ctypes.c_size_t, P], I),
         "pcm_voxel_reduce": ([P, I64, P, I, P, P, P, I64, P, P, P, P, P, P, P, P, ctypes.c_size_t, P], I),
+        "pcm_nearest_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_nearest_keys": ([P, I64, P, I64, ctypes.c_float, P, P, P, P], I),
+        "pcm_nearest_find": ([P, I64, P, I64, P, P, ctypes.c_float, P, P, P, P, P, P, P, P, ctypes.c_size_t, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

@@ -535,10 +535,62 @@ def _gpu_assign(X, C: np.ndarray):
         return res.labels.cpu().numpy(), res.distance.cpu().numpy(), float(res.inertia)
 
 
+def _gpu_nearest(X: np.ndarray, Y: np.ndarray, max_dist: float):
+    """Host (n, 3) and (m, 3) float32 rows -> (index int32 (n,), squared distance float32 (n,)) of
+    ``nearest_points``: the nearest row of ``Y`` within ``max_dist``, -1 / +inf when there is none."""
+    import torch
+
+    from .nearest import nearest_points
+
+    with _gpu_lock:
+        near = nearest_points(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda(),
+                              torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).cuda(), max_dist)
+        return near.index.cpu().numpy(), near.sqdist.cpu().numpy()
+
+
+def _change_args(change, change_to, model):
+    """``change=max_dist`` and its reference points -> (max_dist as a float, the reference rows float32 (M, 3)), checked."""
+    try:
+        with np.errstate(over="ignore", under="ignore"):
+            r = np.float32(change)
+            r2 = np.float32(r * r)
+    except (TypeError, ValueError):
+        r = r2 = np.float32(np.nan)
+    if not (np.isfinite(r) and r > 0 and np.isfinite(r2) and r2 > 0):
+        raise ValueError(f"change must be None or a max_dist finite and > 0 in float32 (and its square), got {change!r}")
+    ref = change_to
+    if ref is None and isinstance(model, dict):
+        ref = model.get("points")
+    if ref is None:
+        raise ValueError("change= needs reference points: pass change_to= (an (M, 3) array or a list of clouds, "
+                         "z, y, x) or a model that carries its points (export_fused / load_fused)")
+    if isinstance(ref, (list, tuple)):
+        parts = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in ref if np.asarray(c).size]
+        ref = np.concatenate(parts) if parts else np.zeros((0, 3))
+    ref = np.asarray(ref, dtype=np.float64)
+    if ref.ndim != 2 or ref.shape[1] != 3:
+        raise ValueError(f"change_to must be an (M, 3) array or a list of (M_i, 3) clouds, got shape {ref.shape}")
+    return float(r), np.ascontiguousarray(ref.astype(np.float32))          # boundary cast (SURVEY.md a4)
+
+
+def _change(X: np.ndarray, ref: np.ndarray, max_dist: float, nearest: Optional[Callable]):
+    """The cloud-to-cloud distance of the labelled rows ``X`` to ``ref`` -> the ``change`` result dict."""
+    index, sq = (nearest or _gpu_nearest)(X, ref, max_dist)
+    index = np.asarray(index).astype(np.int32)
+    sq = np.asarray(sq, dtype=np.float32)
+    if index.shape != (X.shape[0],) or sq.shape != (X.shape[0],) or (index.size and not -1 <= index.min() <= index.max() < max(ref.shape[0], 1)):
+        raise ValueError("nearest must return (index (n,) in [-1, M), squared distance (n,))")
+    found = index >= 0
+    distance = np.where(found, np.sqrt(sq.astype(np.float64)), np.nan)
+    dz = np.full(X.shape[0], np.nan)
+    dz[found] = X[found, 0].astype(np.float64) - ref[index[found], 0].astype(np.float64)
+    return dict(index=index, distance=distance, dz=dz, max_dist=max_dist, found=found)
+
+
 def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None,
                   describe: bool = False, stats: Optional[Callable] = None, register: Optional[str] = None,
                   register_max_dist: Optional[float] = None, align: Optional[Callable] = None, denoise=None,
-                  support: Optional[Callable] = None):
+                  support: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None):
     """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
 
     ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
@@ -565,6 +617,15 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     with fewer than ``min_neighbors`` other rows within ``radius`` -- the later day is filtered
     by its own counts, as one group; a ``min_days`` above 1 raises ValueError -- and labels the
     rest.  ``result`` gains ``denoise`` as in ``kmeans_fuse``; ``support``: the test stand-in.
+
+    ``change`` = ``max_dist`` adds the cloud-to-cloud distance (``nearest_points``): for every
+    labelled row -- after ``register`` and ``denoise`` -- the nearest reference point within
+    ``max_dist``.  The reference points are ``change_to`` (an (M, 3) array or a list of clouds, z, y,
+    x) or, without it, the model's ``points`` (an ``export_fused`` / ``load_fused`` model carries
+    them); ValueError when neither exists.  The "Assigned" layer gains ``change`` (float64 distance
+    to that point, NaN beyond ``max_dist``) and ``change_dz`` (the row's z minus that point's z, NaN
+    likewise); ``result`` gains ``change`` = dict(index, distance, dz, max_dist, found).
+    ``nearest``: the test stand-in (X, Y, max_dist) -> (index, squared distance).
     """
     if not isinstance(model, dict):
         model = load_fused(model)
@@ -576,6 +637,9 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
         raise ValueError("no point cloud layers to assign")
     if denoise is not None:
         _denoise_args(denoise, False)
+    if change is not None:
+        # a bad change= fails before anything is labelled
+        change_dist, change_ref = _change_args(change, change_to, model)
     registration = None
     if register is not None:
         clouds, registration = _register_clouds(clouds, C, None, register, register_max_dist, align)
@@ -592,10 +656,15 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     labels, sq, inertia = (assign or _gpu_assign)(Xq, C)
     labels = np.asarray(labels).astype(np.int32)
     residual = np.sqrt(np.asarray(sq, dtype=np.float64))
+    props = {"cluster": labels, "residual": residual, "height": _norm(X[:, 0].astype(np.float64))}
+    changed = None
+    if change is not None:
+        changed = _change(X, change_ref, change_dist, nearest)
+        props.update(change=changed["distance"], change_dz=changed["dz"])
     layers = [
         (X.astype(np.float64),
          {"name": f"{PREFIX} Assigned {CLOUD_LAYER_SUFFIX}", "size": 2,
-          "properties": {"cluster": labels, "residual": residual, "height": _norm(X[:, 0].astype(np.float64))},
+          "properties": props,
           "scale": (1, 1, 1), "opacity": 0.8, "face_colormap": "turbo", "face_color": "cluster"},
          "points"),
     ]
@@ -604,6 +673,8 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
         result["registration"] = registration
     if denoised is not None:
         result["denoise"] = denoised
+    if changed is not None:
+        result["change"] = changed
     if describe:
         k = C.shape[0]
         st = _describe(X, labels, [X.shape[0]], k, Xq if (stats is None and Xq is not X) else X, stats)
@@ -632,8 +703,12 @@ class HeightMapExtractor(SatellitePlugin):
                  height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                  register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
                  align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None, voxel=None,
-                 voxels: Optional[Callable] = None):
+                 voxels: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None):
         self._base = base
+        # change: add the cloud-to-cloud distance to the assigned layer (kmeans_assign change=); nearest: test stand-in
+        self.change = change
+        self.change_to = change_to
+        self._nearest = nearest
         # voxel: thin every cloud onto a lattice before the fit (kmeans_fuse voxel=); voxels: test stand-in
         self.voxel = voxel
         self._voxels = voxels
@@ -697,7 +772,9 @@ class HeightMapExtractor(SatellitePlugin):
                                                        describe=self.describe, stats=self._stats,
                                                        register=self.register,
                                                        register_max_dist=self.register_max_dist, align=self._align,
-                                              denoise=self.denoise, support=self._support)
+                                              denoise=self.denoise, support=self._support,
+                                                       change=self.change, change_to=self.change_to,
+                                                       nearest=self._nearest)
             return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
@@ -750,7 +827,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                            register=self.register,
                                                            register_max_dist=self.register_max_dist,
                                                            align=self._align, denoise=self.denoise,
-                                                           support=self._support)
+                                                           support=self._support, change=self.change,
+                                                           change_to=self.change_to, nearest=self._nearest)
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path,

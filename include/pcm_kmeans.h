@@ -510,6 +510,66 @@ int pcm_voxel_reduce(const float *X, int64_t n, const uint8_t *groups /* nullabl
                      int64_t *cells, int32_t *counts, int64_t *sums, int32_t *first, int64_t *day_mask /* nullable */,
                      int32_t *inverse, int64_t *info, const void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------- nearest
+ * Exact nearest row of another cloud within a radius: the cloud-to-cloud
+ * distance (no reference counterpart; DESIGN.md §4 "Nearest").  Queries X
+ * (n rows) and targets Y (m rows): device float32 rows (z, y, x); X and Y may be
+ * the same array.  With r2 = radius * radius (float32; both must be finite and
+ * > 0), target j is a candidate of query i iff both rows are finite, groups[i]
+ * != target_groups[j] (when the two are given; device int32, any values,
+ * compared for equality only) and, in float32, every operation rounded, no
+ * contraction,
+ *   dz = X_i.z - Y_j.z, dy = X_i.y - Y_j.y, dx = X_i.x - Y_j.x,
+ *   d2 = (dz*dz + dy*dy) + dx*dx <= r2.
+ *   index[i]  = the candidate j that minimises (d2, j) lexicographically -- a tie
+ *               in distance goes to the LOWEST target row --, -1 when there is none
+ *   sqdist[i] = that d2, +inf when index[i] = -1
+ * A query with a NaN or Inf coordinate gets -1 / +inf; such a target is never a
+ * candidate.  Three steps, all stream-ordered, no host synchronisation, no
+ * allocation:
+ *   pcm_nearest_keys  fills info (device int64[PCM_NEAREST_INFO_WORDS]) from the
+ *                     box over the finite rows of BOTH clouds and writes xkeys
+ *                     (device int64[n]) and ykeys (device int64[m]) against the
+ *                     same cells: 21 bits per axis, x fastest; 2^63 - 1 for a
+ *                     non-finite row;
+ *   (the caller sorts each key array: sorted ascending and its permutation,
+ *    sorted[i] = keys[perm[i]] -- any sort, ties in any order)
+ *   pcm_nearest_find  gathers the cell-sorted copy of Y (planes z, y, x, the row
+ *                     numbers, the int32 groups) into the workspace
+ *                     (pcm_nearest_workspace(m) bytes) and scans: a wave takes 64
+ *                     consecutive sorted queries, read as X[xperm[i]]; writes
+ *                     index (device int32[n]) and sqdist (device float32[n]) in
+ *                     the caller's row order.
+ * info: [0] the cell exponent s (support's rule: the smallest s with 2^s >=
+ * radius (1 + 2^-20), at least -32, raised until |x| 2^-s <= 2^40 and every axis
+ * spans at most 2^21 cells); [1..3] the cell of the box's low corner (z, y, x);
+ * [4..6] the bits each axis needs; [7] the queries skipped as non-finite; [8] the
+ * targets skipped as non-finite; [9..15] internal; [16] set when xperm or yperm
+ * held a value outside its range (that query is left unwritten, that target is
+ * never a candidate).
+ * The results are decided by the predicate and the tie rule alone -- the cells
+ * only prune -- so they are the same bits for any row order, sort and launch
+ * shape.  Cost: a query is tested against every target of the cells around it,
+ * so the work grows with the PRODUCT of the cells' populations.  A cell run
+ * longer than PCM_NEAREST_CHUNK rows is staged in several chunks.
+ * PCM_NEAREST_PHASE=1 / 2 in the environment runs only the gather / only the
+ * scan (measurement).
+ * The arguments are checked before any device call (PCM_E_ARG: n or m < 0 or
+ * >= 2^31, a radius or radius squared not finite or <= 0, one of groups /
+ * target_groups without the other, a null pointer with n or m > 0, a workspace
+ * too small).  n = 0 makes no device call in pcm_nearest_find; m = 0 writes
+ * -1 / +inf for every query without a scan. */
+#define PCM_NEAREST_CHUNK 128
+#define PCM_NEAREST_TPB 256
+#define PCM_NEAREST_INFO_WORDS 20
+int pcm_nearest_workspace(int64_t m, size_t *bytes);
+int pcm_nearest_keys(const float *X, int64_t n, const float *Y, int64_t m, float radius, int64_t *xkeys, int64_t *ykeys,
+                     int64_t *info, void *stream);
+int pcm_nearest_find(const float *X, int64_t n, const float *Y, int64_t m, const int32_t *groups /* nullable */,
+                     const int32_t *target_groups /* nullable */, float radius, const int64_t *xkeys_sorted,
+                     const int64_t *xperm, const int64_t *ykeys_sorted, const int64_t *yperm, int32_t *index,
+                     float *sqdist, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
