@@ -28,6 +28,8 @@ filter_outliers(X, radius, min_neighbors, min_days=)   -> bool keep mask: the ra
 voxel_grid(X, voxel, origin=, groups=, q=)             -> Voxels: exact per-voxel count, centroid sums, lowest row and day mask
 voxel_downsample(X, voxel, mode=, min_count=, min_days=) -> Downsampled: one point per occupied voxel (thinning, persistence filter)
 nearest_points(X, Y, max_dist, groups=, target_groups=) -> Nearest: exact nearest row of another cloud within a radius, its squared distance
+local_moments(X, radius, targets=, q=)                 -> LocalMoments: exact per-row count, offset sums and second moments of the rows within a radius
+point_normals(X, radius, targets=, min_count=)         -> PointNormals: per-row plane normal, point-to-plane distance, roughness, planarity
 HeightMapExtractor                                     -> SatellitePlugin drop-in
 Engine                                                 -> the C-ABI engine wrapper
 """
@@ -40,7 +42,8 @@ __all__ = ["lloyd_fit", "LloydResult", "fixed_q", "QBITS", "Engine", "kmeans_fus
            "dense_transform", "DensePrediction", "kmeans_assign", "cluster_stats", "ClusterStats", "surface_elements",
            "SurfaceElements", "height_grid", "HeightGrid", "align_stats", "AlignStats", "register_days", "Registration",
            "apply_registration", "radius_support", "filter_outliers", "Support", "voxel_grid",
-           "voxel_downsample", "Voxels", "Downsampled", "nearest_points", "Nearest"]
+           "voxel_downsample", "Voxels", "Downsampled", "nearest_points", "Nearest",
+           "local_moments", "point_normals", "LocalMoments", "PointNormals"]
 
 
 def __getattr__(name):
@@ -72,6 +75,9 @@ def __getattr__(name):
     if name in ("nearest_points", "Nearest"):
         from . import nearest
         return getattr(nearest, name)
+    if name in ("local_moments", "point_normals", "LocalMoments", "PointNormals"):
+        from . import moments
+        return getattr(moments, name)
     if name == "KMeans":
         from .estimator import KMeans
         return KMeans

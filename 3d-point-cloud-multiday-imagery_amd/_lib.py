@@ -19,7 +19,7 @@ UNITS = [os.path.join(PKG_DIR, "csrc", u) for u in (
     # the Lloyd engine's host units ("Host units"), the slowest to compile first
     "pcm_engine.hip", "pcm_layout.hip", "pcm_kpp.hip", "pcm_predict.hip", "pcm_inspect.hip", "pcm_cloud.hip",
     "pcm_dense.hip", "pcm_stereo.hip", "pcm_shard.hip", "pcm_xchg.hip", "pcm_stats.hip", "pcm_grid.hip", "pcm_align.hip",
-    "pcm_support.hip", "pcm_voxel.hip", "pcm_nearest.hip")]
+    "pcm_support.hip", "pcm_voxel.hip", "pcm_nearest.hip", "pcm_moments.hip")]
 
 
 def _deps(path, seen):
@@ -70,6 +70,7 @@ EXPORTS = [
     "pcm_support_workspace", "pcm_support_keys", "pcm_support_count",
     "pcm_voxel_workspace", "pcm_voxel_keys", "pcm_voxel_count", "pcm_voxel_reduce",
     "pcm_nearest_workspace", "pcm_nearest_keys", "pcm_nearest_find",
+    "pcm_moments_workspace", "pcm_moments_scan", "pcm_moments_planes",
 ]
 ABI_VERSION = 8
 DENSE_PREDICT_WS = 256   # PCM_DENSE_PREDICT_WS
@@ -91,6 +92,9 @@ VOXEL_E_SPAN = 4         # PCM_VOXEL_E_SPAN: an axis spans more than 2^21 cells
 NEAREST_CHUNK = 128      # PCM_NEAREST_CHUNK: target rows staged through LDS at a time
 NEAREST_TPB = 256        # PCM_NEAREST_TPB: threads per block of the scan kernel
 NEAREST_INFO_WORDS = 20  # PCM_NEAREST_INFO_WORDS
+MOMENTS_CHUNK = 128      # PCM_MOMENTS_CHUNK: target rows staged through LDS at a time
+MOMENTS_TPB = 256        # PCM_MOMENTS_TPB: threads per block of the scan and plane kernels
+MOMENTS_WORDS = 10       # PCM_MOMENTS_WORDS: count, three sums, six products
 
 
 def stats_words(d: int) -> int:
@@ -248,6 +252,9 @@ def _declare(lib):
         "pcm_nearest_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
         "pcm_nearest_keys": ([P, I64, P, I64, ctypes.c_float, P, P, P, P], I),
         "pcm_nearest_find": ([P, I64, P, I64, P, P, ctypes.c_float, P, P, P, P, P, P, P, P, ctypes.c_size_t, P], I),
+        "pcm_moments_workspace": ([I64, ctypes.POINTER(ctypes.c_size_t)], I),
+        "pcm_moments_scan": ([P, I64, P, I64, ctypes.c_float, P, P, P, P, P, P, P, P, ctypes.c_size_t, P], I),
+        "pcm_moments_planes": ([P, I64, P, I64, P, P, P, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)

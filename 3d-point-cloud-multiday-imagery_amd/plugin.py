@@ -548,8 +548,9 @@ def _gpu_nearest(X: np.ndarray, Y: np.ndarray, max_dist: float):
         return near.index.cpu().numpy(), near.sqdist.cpu().numpy()
 
 
-def _change_args(change, change_to, model):
-    """``change=max_dist`` and its reference points -> (max_dist as a float, the reference rows float32 (M, 3)), checked."""
+def _change_args(change, change_to, model, name: str = "change"):
+    """``change=max_dist`` (or ``change_plane=radius``) and its reference points -> (the distance as a float, the
+    reference rows float32 (M, 3)), checked."""
     try:
         with np.errstate(over="ignore", under="ignore"):
             r = np.float32(change)
@@ -557,12 +558,13 @@ def _change_args(change, change_to, model):
     except (TypeError, ValueError):
         r = r2 = np.float32(np.nan)
     if not (np.isfinite(r) and r > 0 and np.isfinite(r2) and r2 > 0):
-        raise ValueError(f"change must be None or a max_dist finite and > 0 in float32 (and its square), got {change!r}")
+        raise ValueError(f"{name} must be None or a {'max_dist' if name == 'change' else 'radius'} finite and > 0 in "
+                         f"float32 (and its square), got {change!r}")
     ref = change_to
     if ref is None and isinstance(model, dict):
         ref = model.get("points")
     if ref is None:
-        raise ValueError("change= needs reference points: pass change_to= (an (M, 3) array or a list of clouds, "
+        raise ValueError(f"{name}= needs reference points: pass change_to= (an (M, 3) array or a list of clouds, "
                          "z, y, x) or a model that carries its points (export_fused / load_fused)")
     if isinstance(ref, (list, tuple)):
         parts = [np.asarray(c, dtype=np.float64).reshape(-1, 3) for c in ref if np.asarray(c).size]
@@ -587,10 +589,38 @@ def _change(X: np.ndarray, ref: np.ndarray, max_dist: float, nearest: Optional[C
     return dict(index=index, distance=distance, dz=dz, max_dist=max_dist, found=found)
 
 
+def _gpu_planes(X: np.ndarray, Y: np.ndarray, radius: float):
+    """Host (n, 3) and (m, 3) float32 rows -> (distance float32 (n,), normal float32 (n, 3), count int64 (n,)) of
+    ``point_normals(X, radius, targets=Y)``: the plane through the rows of ``Y`` within ``radius`` of each row."""
+    import torch
+
+    from .moments import point_normals
+
+    with _gpu_lock:
+        pn = point_normals(torch.from_numpy(np.ascontiguousarray(X, dtype=np.float32)).cuda(), radius,
+                           targets=torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float32)).cuda())
+        return pn.distance.cpu().numpy(), pn.normal.cpu().numpy(), pn.count.cpu().numpy()
+
+
+def _change_plane(X: np.ndarray, ref: np.ndarray, radius: float, planes: Optional[Callable]):
+    """The point-to-plane distance of the labelled rows ``X`` to the local surface of ``ref`` -> the
+    ``change_plane`` result dict."""
+    distance, normal, count = (planes or _gpu_planes)(X, ref, radius)
+    distance, normal = np.asarray(distance, dtype=np.float64), np.asarray(normal, dtype=np.float64)
+    count = np.asarray(count).astype(np.int64)
+    n = X.shape[0]
+    if distance.shape != (n,) or normal.shape != (n, 3) or count.shape != (n,):
+        raise ValueError("planes must return (distance (n,), normal (n, 3), count (n,))")
+    few = count < 3                                          # no plane through fewer than three points
+    return dict(distance=np.where(few, np.nan, distance), normal=np.where(few[:, None], np.nan, normal), count=count,
+                radius=radius)
+
+
 def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable] = None, device_clouds=None,
                   describe: bool = False, stats: Optional[Callable] = None, register: Optional[str] = None,
                   register_max_dist: Optional[float] = None, align: Optional[Callable] = None, denoise=None,
-                  support: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None):
+                  support: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None,
+                  change_plane=None, planes: Optional[Callable] = None):
     """Label per-pair (M_i, 3) z,y,x clouds against a fitted model, without refitting.
 
     ``model``: a ``kmeans_fuse`` result dict, a ``load_fused`` dict, or the path of
@@ -626,6 +656,17 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     to that point, NaN beyond ``max_dist``) and ``change_dz`` (the row's z minus that point's z, NaN
     likewise); ``result`` gains ``change`` = dict(index, distance, dz, max_dist, found).
     ``nearest``: the test stand-in (X, Y, max_dist) -> (index, squared distance).
+
+    ``change_plane`` = ``radius`` adds the change along the surface normal (``point_normals``): for
+    every labelled row -- after ``register`` and ``denoise`` -- the plane through the reference points
+    within ``radius`` of it.  On a sloped surface the distance to the nearest reference POINT is
+    dominated by sampling; the distance to that plane is not.  With or without ``change``; the
+    reference points follow ``change``'s rule (``change_to``, else the model's ``points``, else
+    ValueError).  The "Assigned" layer gains ``change_normal`` (float64: the signed point-to-plane
+    distance, positive above the reference surface, NaN where fewer than 3 reference points lie within
+    ``radius``) and ``change_normal_z`` (the plane normal's z, NaN likewise); ``result`` gains
+    ``change_plane`` = dict(distance, normal, count, radius).  ``planes``: the test stand-in
+    (X, ref, radius) -> (distance, normal, count).
     """
     if not isinstance(model, dict):
         model = load_fused(model)
@@ -640,6 +681,8 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     if change is not None:
         # a bad change= fails before anything is labelled
         change_dist, change_ref = _change_args(change, change_to, model)
+    if change_plane is not None:
+        plane_radius, plane_ref = _change_args(change_plane, change_to, model, "change_plane")
     registration = None
     if register is not None:
         clouds, registration = _register_clouds(clouds, C, None, register, register_max_dist, align)
@@ -661,6 +704,10 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
     if change is not None:
         changed = _change(X, change_ref, change_dist, nearest)
         props.update(change=changed["distance"], change_dz=changed["dz"])
+    plane = None
+    if change_plane is not None:
+        plane = _change_plane(X, plane_ref, plane_radius, planes)
+        props.update(change_normal=plane["distance"], change_normal_z=plane["normal"][:, 0])
     layers = [
         (X.astype(np.float64),
          {"name": f"{PREFIX} Assigned {CLOUD_LAYER_SUFFIX}", "size": 2,
@@ -675,6 +722,8 @@ def kmeans_assign(clouds: Sequence[np.ndarray], model, assign: Optional[Callable
         result["denoise"] = denoised
     if changed is not None:
         result["change"] = changed
+    if plane is not None:
+        result["change_plane"] = plane
     if describe:
         k = C.shape[0]
         st = _describe(X, labels, [X.shape[0]], k, Xq if (stats is None and Xq is not X) else X, stats)
@@ -703,8 +752,12 @@ class HeightMapExtractor(SatellitePlugin):
                  height_map: bool = False, height_map_cell_log2: int = 0, grid: Optional[Callable] = None,
                  register: Optional[str] = None, register_to: int = 0, register_max_dist: Optional[float] = None,
                  align: Optional[Callable] = None, denoise=None, support: Optional[Callable] = None, voxel=None,
-                 voxels: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None):
+                 voxels: Optional[Callable] = None, change=None, change_to=None, nearest: Optional[Callable] = None,
+                 change_plane=None, planes: Optional[Callable] = None):
         self._base = base
+        # change_plane: add the point-to-plane distance to the assigned layer (kmeans_assign change_plane=); planes: test stand-in
+        self.change_plane = change_plane
+        self._planes = planes
         # change: add the cloud-to-cloud distance to the assigned layer (kmeans_assign change=); nearest: test stand-in
         self.change = change
         self.change_to = change_to
@@ -774,7 +827,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                        register_max_dist=self.register_max_dist, align=self._align,
                                               denoise=self.denoise, support=self._support,
                                                        change=self.change, change_to=self.change_to,
-                                                       nearest=self._nearest)
+                                                       nearest=self._nearest, change_plane=self.change_plane,
+                                                       planes=self._planes)
             return layers + assigned
         use_dev = self._fit is None and all(d is not None for d in dev_clouds)
         fused, self.last_result = kmeans_fuse(host_clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
@@ -828,7 +882,8 @@ class HeightMapExtractor(SatellitePlugin):
                                                            register_max_dist=self.register_max_dist,
                                                            align=self._align, denoise=self.denoise,
                                                            support=self._support, change=self.change,
-                                                           change_to=self.change_to, nearest=self._nearest)
+                                                           change_to=self.change_to, nearest=self._nearest,
+                                                           change_plane=self.change_plane, planes=self._planes)
                 return layers + assigned
             fused, self.last_result = kmeans_fuse(clouds, self.n_clusters, self.max_iter, self.tol, seed=self.seed,
                                                   fit=self._fit, init=self.init, export_path=self.export_path,

@@ -570,6 +570,70 @@ int pcm_nearest_find(const float *X, int64_t n, const float *Y, int64_t m, const
                      const int64_t *xperm, const int64_t *ykeys_sorted, const int64_t *yperm, int32_t *index,
                      float *sqdist, int64_t *info, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------- local moments
+ * Exact per-point neighbourhood moments and the plane through a point's
+ * neighbours (no reference counterpart; DESIGN.md §4 "Local moments").  Queries
+ * X (n rows) and targets Y (m rows): device float32 rows (z, y, x).  Target j is
+ * in the neighbourhood of query i iff both rows are finite and the predicate of
+ * the nearest section holds (d2 <= r2, float32, no contraction): no groups, no
+ * self-exclusion.  With q (host int32[3], each in [-126, 62]),
+ *   yq_a = trunc(ldexp(Y_j.a, q_a)), xq_a = trunc(ldexp(X_i.a, q_a)), dq_a = yq_a - xq_a
+ * and words (device int64[n * PCM_MOMENTS_WORDS], row-major) receives per query
+ *   [0] the count   [1..3] sum dq_z, dq_y, dq_x
+ *   [4..9] sum dq_a dq_b for (zz, zy, zx, yy, yx, xx).
+ * Integer sums: the same bits for any row order, sort and launch shape.  A
+ * non-finite query gets ten zeros; a non-finite target is in no neighbourhood.
+ * The kernel checks nothing per pair: the CALLER chooses q so that, with
+ * B_a = floor((double)radius (1 + 2^-20) 2^q_a) + 1 (>= |dq_a| of every pair the
+ * predicate admits), B_a < 2^31, max(m, 1) B_a B_b <= 2^62 and |coordinate_a|
+ * 2^q_a < 2^31 over the finite rows of both clouds.  Steps, all stream-ordered,
+ * no host synchronisation, no allocation:
+ *   pcm_nearest_keys  (above) fills info and the keys of both clouds;
+ *   (the caller sorts each key array, as for pcm_nearest_find)
+ *   pcm_moments_scan  gathers the cell-sorted copy of Y (three float planes and
+ *                     the three int32 fixed-point planes) into the workspace
+ *                     (pcm_moments_workspace(m) bytes) and scans as
+ *                     pcm_nearest_find does: a wave takes 64 consecutive sorted
+ *                     queries, read as X[xperm[i]], and stages the candidates
+ *                     through LDS in chunks of PCM_MOMENTS_CHUNK rows.  info is
+ *                     the block pcm_nearest_keys filled (layout above); a value
+ *                     of xperm or yperm outside its range sets info[16].
+ *                     Y == NULL: the targets are the queries -- m, ykeys_sorted
+ *                     and yperm are ignored (the queries' arrays serve), the
+ *                     workspace is pcm_moments_workspace(n) bytes, and info comes
+ *                     from pcm_nearest_keys(X, n, NULL, 0, ...): the targets
+ *                     skipped are the queries skipped.
+ *   pcm_moments_planes  one lane per row, float64: c = words[0],
+ *                     mu_a = S_a 2^-q_a / c, C_ab = M_ab 2^-(q_a + q_b) / c - mu_a mu_b,
+ *                     eigen-decomposition by cyclic Jacobi (until the
+ *                     off-diagonals are zero, at most 8 sweeps);
+ *                     normal (device float32[n * 3]) the unit eigenvector of the
+ *                     smallest eigenvalue, signed z >= 0, ties by y then x (a
+ *                     component within 2^-30 of 0 is set to 0 first, so that the
+ *                     rounding noise of a vertical plane's z picks no sign);
+ *                     roughness = sqrt(max(l0, 0)); planarity = (l1 - l0) / l2,
+ *                     0 where l2 <= 0; distance = -normal . mu, the signed
+ *                     distance of the query to the plane through the
+ *                     neighbourhood's mean (device float32[n] each).  Rows with
+ *                     count < max(min_count, 1) get NaN.
+ * PCM_MOMENTS_PHASE=1 / 2 in the environment runs only the gather / only the
+ * scan (measurement).  Cost: as for nearest, the work grows with the PRODUCT of
+ * the cells' populations.
+ * The arguments are checked before any device call (PCM_E_ARG: n or m < 0 or
+ * >= 2^31, a radius or radius squared not finite or <= 0, q null or outside
+ * [-126, 62], min_count < 0, a null pointer, a workspace too small).  n = 0
+ * makes no device call; m = 0 (Y not NULL) zeroes words without a scan. */
+#define PCM_MOMENTS_CHUNK 128
+#define PCM_MOMENTS_TPB 256
+#define PCM_MOMENTS_WORDS 10
+int pcm_moments_workspace(int64_t m, size_t *bytes);
+int pcm_moments_scan(const float *X, int64_t n, const float *Y /* nullable: the queries */, int64_t m, float radius,
+                     const int32_t *q /* host int32[3] */, const int64_t *xkeys_sorted, const int64_t *xperm,
+                     const int64_t *ykeys_sorted, const int64_t *yperm, int64_t *words, int64_t *info, void *workspace,
+                     size_t workspace_bytes, void *stream);
+int pcm_moments_planes(const int64_t *words, int64_t n, const int32_t *q /* host int32[3] */, int64_t min_count,
+                       float *normal, float *distance, float *roughness, float *planarity, void *stream);
+
 /* ---------------------------------------------------------------- slab sharding
  * Multi-GPU layout (no reference counterpart -- the reference is
  * single-process): the row shards the ranks receive are regrouped into slabs
